@@ -10,14 +10,20 @@ fetal-monitoring windows (vaeteb.synthetic; the clinical HDF5 records are not
 available), weights are the reference architecture's random init.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--frontend j11|j6] [--batch B] [--workload c2|c4|c5]
+                  [--dump-outputs DIR] [--full]
   N > 1: either form works —
     python bench.py --gpus N          (starts N rank processes itself, vaeteb.train.spawn_local_ranks)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
   VAETEB_DIST_BACKEND=gloo: gloo instead of RCCL, ranks share the visible GPUs (one-GPU rehearsal)
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, timed
-live with HIP events on its own stream inside the timed region; `cpu_baseline`
-is the oracle (faithful CPU restatement) on a bounded sample, rank 0 / N = 1 only.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+reports what the timed region itself measured: the headline figure, `ms_per_step`, the
+last step's losses and `roofline` for the dominant kernel (timed live with HIP events on
+its own stream inside the timed region).  --dump-outputs DIR also writes what the last
+timed step returned (DIR/<name>.npy, see dump_outputs).  --full adds everything that takes
+work outside the timed steps: `cpu_baseline` (the oracle, a faithful CPU restatement, on a
+bounded sample, rank 0 / N = 1 only), `mfma` (extra eager steps after the timed region)
+and the figures read from the committed profiles (`traffic`, `hbm_kernels`, `lstm`).
 """
 import argparse
 import json
@@ -279,6 +285,36 @@ def _json_stdout():
     return os.fdopen(saved, "w")
 
 
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs: all files together
+DUMP_SAMPLE_ELEMS = 4 << 20    # elements kept of a larger array (16 MiB in fp32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: write what the last timed step handed to its caller as DIR/<name>.npy
+    (float32; float64 stays float64).  An array of more than 4 Mi elements is written as a
+    fixed sample of its flattened elements instead: the values at the sorted indices that
+    numpy's default_rng(0).integers(0, numel, 4 Mi) draws, the same for every run and build.
+    DIR/manifest.json records every array's full shape and whether it was sampled; all files
+    together stay under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    manifest, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": False}
+        if t.numel() > DUMP_SAMPLE_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry["sampled"] = True
+        a = t.contiguous().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {name} takes the dump past {DUMP_MAX_BYTES} bytes"
+        np.save(os.path.join(path, name + ".npy"), a)
+        manifest[name] = entry
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def run_c5(args, rank, world, dev):
     """Config 5 (BASELINE.json configs[4]): long-sequence stress, front-end only —
     Scattering1D(J=8, Q=12, T=256, order 2) on 16384-point windows, batch 64 per
@@ -314,13 +350,16 @@ def run_c5(args, rank, world, dev):
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"S": S})   # the last timed step's coefficients (B, 337, 64)
     k_ms, k_n = timer.mean_ms("vt_scat_mod_spec")
     k_bytes = timer.total_flops["vt_scat_mod_spec"] / max(k_n, 1)
     achieved = k_bytes / (k_ms * 1e-3) / 1e9
-    # PMC traffic of the same kernel from separate FETCH_SIZE / WRITE_SIZE passes of this command
-    # (profiles/rNN/pmc_traffic_c5.json): an average over the launches of the cascade's levels,
-    # quoted for the default geometry only
-    traffic, traffic_src = pmc_traffic("k_scat_mod_spec", "pmc_traffic_c5.json") if B == 64 else (None, None)
+    # --full: PMC traffic of the same kernel from separate FETCH_SIZE / WRITE_SIZE passes of this
+    # command (profiles/rNN/pmc_traffic_c5.json): an average over the launches of the cascade's
+    # levels, quoted for the default geometry only
+    traffic, traffic_src = (pmc_traffic("k_scat_mod_spec", "pmc_traffic_c5.json") if B == 64 and args.full
+                            else (None, None))
     out = {"metric": "scattering samples/sec, Scattering1D(J=8, Q=12) 16384-pt windows, batch 64/GPU",
            "value": round(args.steps * B * world / dt, 3), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
@@ -334,7 +373,7 @@ def run_c5(args, rank, world, dev):
                         "traffic_source": traffic_src, "avg_launch_ms": round(k_ms, 4), "launches": k_n,
                         "algorithmic_bytes": round(k_bytes)},
            "checksum": float(S.double().abs().sum().item())}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         from oracle import frontend_ref as F
         xs = pool[0].cpu().numpy()   # the whole batch
@@ -366,7 +405,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--frontend", choices=list(FRONTENDS), default="j11")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes work outside the timed steps: the CPU baseline (the oracle's "
+                         "step on a bounded sample), the decoder heads' MFMA figures (extra eager steps after the "
+                         "timed region) and the figures read from the committed profiles (PMC traffic, per-family "
+                         "HBM rates, the LSTMs' critical-chain share).  Default: set up, warm up, time the steps, "
+                         "print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(c2 / c4: the step's losses and the parameters it left, c5: the scattering "
+                         "coefficients; rank 0) and DIR/manifest.json; see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--graph", action="store_true",
                     help="= --mode graph: the model step replayed as a captured hipGraph (double-buffered, "
@@ -638,14 +687,20 @@ def main():
     keys = ("total_loss", "classification_loss", "vae_loss") if c4 else ("total_loss", "nll_loss", "mse_loss",
                                                                           "kld_loss")
     elbo = {k: round(float(last[k].item()), 6) for k in keys}
+    if args.dump_outputs and rank == 0:
+        # what the step hands to its caller: the loss terms it returns and the parameters it
+        # updated in place (the flat fp32 vector of the model's parameters, sampled)
+        dump_outputs(args.dump_outputs, {**{k: v for k, v in last.items() if isinstance(v, torch.Tensor)},
+                                         "params": trainer.state.p})
     samples = args.steps * B * world
     value = samples / dt
     n_params = sum(p.numel() for p in model.parameters())
     step_bytes = step_bytes_per_sample(plan, fe, n_params, B)
     fe_timed_in = "timed region"
-    if graph and args.native and fe_in_graph:
+    if graph and args.native and fe_in_graph and args.full:
         # the front-end runs inside the replay: time its kernel in two eager steps after the
-        # timed region (the same kernels and shapes; profiles/ holds the in-replay durations)
+        # timed region (the same kernels and shapes; profiles/ holds the in-replay durations);
+        # a run without --full has no launch of it to time and prints no `roofline`
         timer.reset(True)
         for i in range(2):
             trainer.step({"x": pool[i % 2], **({"labels": labels[i % 2]} if c4 else {})})
@@ -656,8 +711,8 @@ def main():
     k_bytes = timer.total_flops["vt_fe_pairs"] / max(k_n, 1)   # mean algorithmic bytes per launch
     # the PMC passes ran the default command (native replay, one launch of all pairs per step):
     # only a run with that launch shape quotes their traffic
-    traffic, traffic_src = (pmc_traffic("k_fe_pairs8k") if (J, Q, T, B) == (11, 4, 16, 256) and args.native
-                            else (None, None))
+    traffic, traffic_src = (pmc_traffic("k_fe_pairs8k")
+                            if (J, Q, T, B) == (11, 4, 16, 256) and args.native and args.full else (None, None))
     achieved = k_bytes / (k_ms * 1e-3) / 1e9
     out = {
         "metric": "train samples/sec + ELBO, 4096-pt windows, batch 256, 1/2/4/8 MI355X",
@@ -719,6 +774,15 @@ def main():
     }
     if dist.is_initialized():
         out["dist_backend"] = dist.get_backend()   # "nccl" = RCCL on ROCm
+    if not k_n:
+        del out["roofline"]   # no launch of the pair kernel was timed (--fe-in-graph 1 without --full)
+    if not args.full:
+        # a plain run ends here: everything above was measured inside the timed region
+        if rank == 0:
+            print(json.dumps(out), file=OUT, flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     hbm = pmc_kernels() if (J, Q, T, B) == (11, 4, 16, 256) and not c4 else None
     if hbm:
         out["hbm_kernels"] = hbm

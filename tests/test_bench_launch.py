@@ -87,3 +87,48 @@ def test_init_distributed_backend_override(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "1")
     monkeypatch.setenv("LOCAL_RANK", "0")
     assert init_distributed()[:3] == (0, 1, 0)
+
+
+def test_dump_outputs_files_sample_and_size_cap(tmp_path):
+    """bench.py --dump-outputs: every array as float32 (float64 kept) in DIR/<name>.npy with its
+    own shape; an array of more than DUMP_SAMPLE_ELEMS elements as the fixed seeded sample of its
+    flattened elements, identical from call to call; the manifest records the full shapes; a
+    dump that would pass 64 MB is refused."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_SAMPLE_ELEMS + 12345
+    big = torch.arange(n, dtype=torch.float32)
+    arrays = {"loss": torch.tensor(1.5), "pred": torch.arange(6).reshape(2, 3), "d": torch.ones(3, dtype=torch.float64),
+              "half": torch.full((4,), 0.5, dtype=torch.bfloat16), "params": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert got["loss"].shape == () and got["loss"].dtype == np.float32 and got["loss"] == 1.5
+    assert got["pred"].dtype == np.float32 and (got["pred"] == np.arange(6).reshape(2, 3)).all()
+    assert got["d"].dtype == np.float64 and got["half"].dtype == np.float32 and (got["half"] == 0.5).all()
+    idx = got["params"].astype(np.int64)          # arange: the sampled values are their own indices
+    assert idx.shape == (bench.DUMP_SAMPLE_ELEMS,) and (np.diff(idx) >= 0).all() and 0 <= idx[0] and idx[-1] < n
+    assert len(np.unique(idx)) > 0.5 * len(idx)   # spread over the array, not one block
+    assert (np.load(tmp_path / "b" / "params.npy") == got["params"]).all()
+    man = json.load(open(tmp_path / "a" / "manifest.json"))
+    assert man["params"] == {"shape": [n], "dtype": "float32", "sampled": True}
+    assert man["pred"] == {"shape": [2, 3], "dtype": "float32", "sampled": False}
+    files = [f for f in os.listdir(tmp_path / "a") if f.endswith(".npy")]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    with pytest.raises(AssertionError, match="dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "c"), {f"p{i}": big.double() for i in range(3)})
+
+
+def test_bench_full_and_dump_outputs_reach_the_ranks(monkeypatch):
+    """--full and --dump-outputs reach the rank processes like every other argument."""
+    sys.path.insert(0, ROOT)
+    import bench
+    calls = []
+    monkeypatch.setattr(bench, "spawn_local_ranks", lambda cmd, n: calls.append(cmd) or 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full", "--dump-outputs", "d"])
+    with pytest.raises(SystemExit):
+        bench.main()
+    assert calls[0][2:] == ["--gpus", "2", "--full", "--dump-outputs", "d"]

@@ -9,9 +9,9 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --time
 kill $hb
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || exit $?
-timeout -k 10 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err || exit $?
-timeout -k 10 300 python bench.py --workload c4 > $out/bench_c4.json 2> $out/bench_c4.err || exit $?
-timeout -k 10 300 python bench.py --workload c5 > $out/bench_c5.json 2> $out/bench_c5.err || exit $?
-timeout -k 10 300 python bench.py --ddp-probe --no-cpu-baseline > $out/bench_ddp_probe.json 2> $out/bench_ddp_probe.err || exit $?
-timeout -k 10 300 python bench.py --frontend j6 --no-cpu-baseline > $out/bench_j6.json 2> $out/bench_j6.err || exit $?
-timeout -k 10 300 python bench.py --precision fp16 --no-cpu-baseline > $out/bench_fp16.json 2> $out/bench_fp16.err
+timeout -k 10 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit $?
+timeout -k 10 300 python bench.py --full --workload c4 > $out/bench_c4.json 2> $out/bench_c4.err || exit $?
+timeout -k 10 300 python bench.py --full --workload c5 > $out/bench_c5.json 2> $out/bench_c5.err || exit $?
+timeout -k 10 300 python bench.py --full --ddp-probe --no-cpu-baseline > $out/bench_ddp_probe.json 2> $out/bench_ddp_probe.err || exit $?
+timeout -k 10 300 python bench.py --full --frontend j6 --no-cpu-baseline > $out/bench_j6.json 2> $out/bench_j6.err || exit $?
+timeout -k 10 300 python bench.py --full --precision fp16 --no-cpu-baseline > $out/bench_fp16.json 2> $out/bench_fp16.err

@@ -9,4 +9,4 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -v -p no:cacheprovider --tim
 kill $hb
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || exit $?
-timeout -k 10 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
