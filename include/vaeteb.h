@@ -162,6 +162,35 @@ int vt_zero_ranges(float* base, int n, const int64_t* starts, const int64_t* end
 int vt_normalize_raw(const float* x, int64_t rows, int64_t row_stride, int N, float mean, float stdv, float* out,
                      void* stream);
 
+/* ------------------------------------------------------- dataset statistics
+ * One pass over the raw fp32 features the front-end leaves on the device, accumulating the
+ * per-channel {count, sum, sum of squares} the normalisation statistics are finalised from
+ * (mean = sum / count, variance = sum_sq / count - mean^2; vaeteb/stats.py finalize_state).
+ * Element (b, c, s) is in[(b*in_C + c)*in_S + s0 + s] as in vt_fe_normalize_window (a channel
+ * sub-view has in_C > C, the dataset trim is s0 / S_len).  kind[c]: 0 regular, 1 log, 2 asinh
+ * (NULL: every channel regular).  Per element, in fp64: x non-finite -> skipped; t = x,
+ * log(max(x,0) + log_eps) or asinh(x); t non-finite -> skipped; else count[c] += 1,
+ * sum[c] += t, sum_sq[c] += t*t.  The state arrays (device, zeroed by the caller) are
+ * added to in place and persist across calls.
+ * Deterministic: a workgroup reduces one channel over VT_STATS_CHUNK_ROWS batch rows x
+ * VT_STATS_CHUNK_COLS steps in a fixed order and writes one partial to `work`; a second
+ * launch adds a channel's partials to the state in index order.  No floating-point atomics;
+ * the chunking depends on the shapes only, so equal inputs give equal bits on any device.
+ * work: vt_stats_workspace_bytes(B, C, S_len) bytes, 8-byte aligned, contents irrelevant.
+ * replaces: _update_multi_channel_stats / _update_single_channel_stats
+ *           (ref/hdf5_dataset/calculate_dataset_stats.py:134-221)                          */
+#define VT_STATS_CHUNK_ROWS 32
+#define VT_STATS_CHUNK_COLS 1024
+int vt_stats_chunking(int* rows, int* cols);
+int vt_stats_workspace_bytes(int64_t B, int C, int S_len, int64_t* bytes);
+int vt_stats_accum(const float* in, int64_t B, int C, int in_C, int in_S, int s0, int S_len, const int* kind,
+                   double log_eps, int64_t* count, double* sum, double* sum_sq, void* work, int64_t work_bytes,
+                   void* stream);
+/* The single-channel form (fhr, up): row r is x + r*row_stride, N samples each; count, sum and
+ * sum_sq are one element.  Workspace: vt_stats_workspace_bytes(rows, 1, N).                 */
+int vt_stats_accum_raw(const float* x, int64_t rows, int64_t row_stride, int N, int64_t* count, double* sum,
+                       double* sum_sq, void* work, int64_t work_bytes, void* stream);
+
 /* kymatio backend-plugin primitives (TorchBackend1D, ref/kymatio/kymatio/scattering1d/
  * backend/torch_backend.py:17-174 and ref/kymatio/kymatio/backend/torch_backend.py:99-219) */
 int vt_fft(const void* in, void* out, int64_t rows, int n, int inverse, const void* tw, int tw_stride,

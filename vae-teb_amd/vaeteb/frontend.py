@@ -183,6 +183,7 @@ class FrontEnd:
         self.C_st = 1 + p.n_filters
         self.C_ph, self.C_x = len(self.phase_pairs), len(self.cross_pairs)
         self.stats = None
+        self.stats_accumulator = None   # the StatsAccumulator of the last fit_stats
         if stats is not None:
             self.set_stats(stats)
         self._bufs = {}
@@ -200,6 +201,19 @@ class FrontEnd:
             s[f] = (_i32(k, dev), _f32(m, dev), _f32(np.sqrt(v), dev))
         s["fhr"] = (float(np.asarray(stats["fhr_mean"])), float(np.sqrt(np.asarray(stats["fhr_variance"]))))
         self.stats = s
+
+    def fit_stats(self, batches, side=None):
+        """Compute the normalisation statistics from an iterable of (B, 2, N) window batches
+        on the device (vaeteb.stats.StatsAccumulator: this front-end's raw features, its trim,
+        the reference's formula), install them with set_stats and return the mapping."""
+        from .stats import StatsAccumulator
+        acc = StatsAccumulator.for_frontend(self)
+        for x in batches:
+            acc.update_windows(self, x, side)
+        stats = acc.finalize()
+        self.set_stats(stats)
+        self.stats_accumulator = acc
+        return stats
 
     def _buf(self, name, shape, dtype=torch.float32):
         b = self._bufs.get(name)
