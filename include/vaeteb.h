@@ -703,11 +703,16 @@ int vt_lstm16_pair_fwd(const float* x, int In, const float* w_ih0, const float* 
 /* Its backward: layer l + 1 (dh_out at its outputs, its forward's gates1 / c1) and layer l
  * one chunk behind it, layer l + 1's dX handed to layer l in LDS.  dgates1 / dgates0 and
  * dx (layer l's input gradient [B, S, In0], may be null) are exactly two
- * vt_lstm16_layer_bwd calls', bit for bit.                                          */
+ * vt_lstm16_layer_bwd calls', bit for bit.
+ * dg_bf16 selects each layer's dgates format: bit 0 dgates0, bit 1 dgates1.  Clear: fp32
+ * [B, S, 4 hidden] by gate row, as vt_lstm16_layer_bwd's.  Set: the bf16 image [B, S, 4 hidden]
+ * the recurrence itself works on — column 4 u + g holds gate g of unit u, i.e. fp32 column
+ * g hidden + u rounded to bf16, bit for bit — half the bytes, 8-byte aligned; consumed by
+ * vt_lstm16_bwd_weight_multi (ask vt_lstm16_dg16_ok first).  dx does not depend on it.   */
 int vt_lstm16_pair_bwd(const float* dh_out, const float* gates1, const float* c1, const float* w_hh1,
                        const float* w_ih1, const float* gates0, const float* c0, const float* w_hh0,
-                       const float* w_ih0, int In0, int B, int seq, int hidden, float* dgates1, float* dgates0,
-                       float* dx, void* stream);
+                       const float* w_ih0, int In0, int B, int seq, int hidden, void* dgates1, void* dgates0,
+                       float* dx, void* stream, int dg_bf16);
 /* All four layers of nn.LSTM(num_layers=4) in ONE launch (round 6): the two layer pairs of
  * vt_lstm16_pair_fwd run concurrently, pair 1 (layers 2, 3) consuming layer 1's h chunk by
  * chunk as pair 0 publishes it (a per-chunk flag; agent-coherent stores / loads) — S + 4
@@ -723,9 +728,10 @@ int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B
  * the gradient at layer 1's outputs, written to dmid [B, S, hidden] — chunk by chunk to layers
  * 1, 0 running concurrently.  w: [w_ih, w_hh] x 4 layers; gc: [gates, c] x 4 layers (the
  * forward's); dg: the 4 layers' dgates [B, S, 4 hidden]; dx: layer 0's input gradient [B, S,
- * In0] (may be null).  Exactly two vt_lstm16_pair_bwd calls', bit for bit.                */
+ * In0] (may be null).  Exactly two vt_lstm16_pair_bwd calls', bit for bit.  dg_bf16: bit l set
+ * = dg[l] is the bf16 image of vt_lstm16_pair_bwd, clear = fp32.                          */
 int vt_lstm16_quad_bwd(const float* dh_out, const float* const* w, const float* const* gc, int In0, int B, int seq,
-                       int hidden, float* const* dg, float* dmid, float* dx, void* stream);
+                       int hidden, void* const* dg, float* dmid, float* dx, void* stream, int dg_bf16);
 /* Timeouts of the chained launches' bounded waits since the last reset (0 unless a producer
  * workgroup could not run; host-synchronous diagnostic).                                  */
 int vt_lstm16_chain_errors(int* count, int reset);
@@ -741,6 +747,26 @@ int vt_lstm_layer_bwd_weight(const float* dgates, const float* x, int In, const 
 int vt_lstm16_layer_bwd_weight(const float* dgates, const float* x, int In, const float* h, int B, int S,
                                int hidden, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int accumulate,
                                float* ws, int64_t ws_floats, void* stream);
+/* 1 when the bf16 weight-gradient kernel takes a layer of input size In (In % 4 == 0, In <= 64,
+ * VAETEB_L16_DW16 not 0) — only then may its dgates be handed over as the bf16 image; else 0
+ * (not an error code).                                                                      */
+int vt_lstm16_dg16_ok(int In);
+/* The parameter gradients of nl (1..4) layers over the same B x S rows in one launch plus one
+ * fixed-order sum (no atomics: deterministic).  Per layer l: dgates[l] fp32 [B*S, 4 hidden]
+ * (dg_bf16[l] = 0) or the bf16 image of vt_lstm16_pair_bwd (dg_bf16[l] = 1), x[l] [B*S, In[l]],
+ * h[l] [B*S, hidden] (h_{t-1} read one row back, zero at t = 0), grads[4 l .. 4 l + 3] = dw_ih,
+ * dw_hh, db_ih, db_hh (the last may be null), accumulate[l].  All arrays are host arrays.
+ *   [dw_ih | dw_hh | db] (+)= bf16(dgates)^T bf16([x | h_{t-1} | 1]), fp32 accumulation.
+ * A layer's row partition and summation order depend on B * S alone: its result does not
+ * depend on its dgates format, on the other layers of the call or on its place among them, and
+ * equals vt_lstm16_layer_bwd_weight's, bit for bit.  A layer the bf16 kernel does not take
+ * (vt_lstm16_dg16_ok, or operands not 16-byte aligned) must come with fp32 dgates and runs on
+ * the exact-fp32 kernel after the others.  ws: at least the sum over the layers of
+ * min(128, ceil(B*S / 256)) * 4 hidden * (In[l] + hidden + 1) floats (the fp32 kernel: as
+ * vt_lstm_layer_bwd_weight).                                                               */
+int vt_lstm16_bwd_weight_multi(int nl, const void* const* dgates, const int* dg_bf16, const float* const* x,
+                               const int* In, const float* const* h, int B, int seq, int hidden, float* const* grads,
+                               const int* accumulate, float* ws, int64_t ws_floats, void* stream);
 
 /* ---------------------------------------------------------- classifier (c4)
  * FHRInceptionTimeClassifier (ref/model/inception_time.py:185-333) on

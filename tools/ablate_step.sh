@@ -8,7 +8,7 @@ for cfg in base vt_fe_pairs vt_fe_wavelet vt_resmlp_bf16_bwd vt_resmlp_bf16_fwd 
            vt_lstm16_pair_fwd vt_batchnorm_bwd_coef,vt_batchnorm_bwd_x16 vt_conv1d_bwd_dx16 \
            vt_conv1d_bwd_weight_bf16_dy16s vt_conv1d_bn_fwd_bf16 \
            vt_mfma_linear_fwd,vt_mfma_linear_bwd_data,vt_mfma_linear_bwd_weight vt_adamw_step_dev_shadow \
-           vt_lstm16_layer_bwd_weight ; do
+           vt_lstm16_bwd_weight_multi ; do
   if [ $cfg = base ]; then ab=""; else ab=$cfg; fi
   VAETEB_ABLATE=$ab timeout -k 10 150 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > gpurun_out/abl/$cfg.json 2> gpurun_out/abl/$cfg.err || exit 1
   echo "$cfg $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/abl/$cfg.json)"

@@ -2,6 +2,8 @@
 vt_lstm16_pair_bwd calls on the same forward state, every output compared separately
 (dgates of layers 3, 2, the hand-off dmid, dgates of layers 1, 0, dx), and the same for the
 forward's 12 outputs.  Prints one line per tensor: equal or the count / max of differences.
+The quad backward then runs once more handing its dgates over as bf16 images (the trailing
+format argument, one bit per layer): each image against the rounded, column-permuted fp32 dgates.
 
   python tools/chain_debug.py [B] [S] [In]
 """
@@ -57,11 +59,11 @@ def main():
     cnt = ctypes.c_int()
     call("vt_lstm16_chain_errors", ctypes.byref(cnt), 1)
     call("vt_lstm16_quad_bwd", ptr(dh), ctypes.addressof(wv), ctypes.addressof(gv), In, B, S, H, ctypes.addressof(dv),
-         ptr(mq), ptr(xq), st())
+         ptr(mq), ptr(xq), st(), 0)
     call("vt_lstm16_pair_bwd", ptr(dh), ptr(g[3]), ptr(c[3]), ptr(P[13]), ptr(P[12]), ptr(g[2]), ptr(c[2]), ptr(P[9]),
-         ptr(P[8]), H, B, S, H, ptr(dgp[3]), ptr(dgp[2]), ptr(mp), st())
+         ptr(P[8]), H, B, S, H, ptr(dgp[3]), ptr(dgp[2]), ptr(mp), st(), 0)
     call("vt_lstm16_pair_bwd", ptr(mp), ptr(g[1]), ptr(c[1]), ptr(P[5]), ptr(P[4]), ptr(g[0]), ptr(c[0]), ptr(P[1]),
-         ptr(P[0]), In, B, S, H, ptr(dgp[1]), ptr(dgp[0]), ptr(xp), st())
+         ptr(P[0]), In, B, S, H, ptr(dgp[1]), ptr(dgp[0]), ptr(xp), st(), 0)
     torch.cuda.synchronize()
     call("vt_lstm16_chain_errors", ctypes.byref(cnt), 1)
     print(f"chain timeouts: {cnt.value}")
@@ -88,6 +90,18 @@ def main():
                     eq = (a[:, :sh] == b[:, -sh:]).float().mean().item()
                 print(f"  dmid(quad)[t] == dmid(pairs)[t - {sh}] fraction {eq:.3f}")
             print("  quad zeros:", (a == 0).float().mean().item(), "pairs zeros:", (b == 0).float().mean().item())
+    # the bf16 hand-off: image column 4 u + g == bf16(dgates[g H + u])
+    img = [torch.empty(B, S, 4 * H, dtype=torch.bfloat16, device="cuda") for _ in range(4)]
+    mi, xi = E(B, S, H), E(B, S, In)
+    iv = (ctypes.c_void_p * 4)(*[ptr(t) for t in img])
+    call("vt_lstm16_quad_bwd", ptr(dh), ctypes.addressof(wv), ctypes.addressof(gv), In, B, S, H, ctypes.addressof(iv),
+         ptr(mi), ptr(xi), st(), 15)
+    torch.cuda.synchronize()
+    for k in range(4):
+        want = dgq[k].view(B, S, 4, H).transpose(-1, -2).reshape(B, S, 4 * H).bfloat16()
+        n = (img[k].view(torch.int16) != want.view(torch.int16)).sum().item()
+        print(f"bwd dg{k} image: {'equal' if n == 0 else f'{n} differ'}")
+    print(f"bwd dmid / dx with images: {'equal' if torch.equal(mi, mq) and torch.equal(xi, xq) else 'DIFFER'}")
 
 
 if __name__ == "__main__":

@@ -1,14 +1,17 @@
 """One LSTM layer of the training geometry (B = 256 samples, S = 256 steps,
 hidden 64, In = 64) alone: vt_lstm_layer_fwd_x, vt_lstm_layer_bwd_x,
 vt_lstm_layer_bwd_weight (HIP events, mean of 10 launches), and the recurrences
-of two layers launched together on two streams (the two encoders)."""
+of two layers launched together on two streams (the two encoders).  With L16=1 also
+the batched weight gradient vt_lstm16_bwd_weight_multi: one layer from fp32 dgates, one layer
+from the bf16 image, and four layers (IN, 64, 64, 64) from images in one call."""
+import ctypes
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vae-teb_amd"))
 import torch  # noqa: E402
-from vaeteb._lib import call, ptr, stream  # noqa: E402
+from vaeteb._lib import call, lib, ptr, stream  # noqa: E402
 
 B, S, H, In = int(os.environ.get("B", "256")), 256, 64, int(os.environ.get("IN", "64"))
 L16 = os.environ.get("L16", "0") == "1"   # the 16-bit MFMA recurrences (vt_lstm16_layer_*)
@@ -97,3 +100,32 @@ def mixed():
 
 
 print(f"In={In} bwd_x || bwd_weight: {timed(mixed):7.1f} us", flush=True)
+
+
+def multi(layers, fmt):
+    n = len(layers)
+    key = "img" if fmt else "dg"
+    dv = (ctypes.c_void_p * n)(*[ptr(t[key]) for t in layers])
+    fv = (ctypes.c_int * n)(*[fmt] * n)
+    xv = (ctypes.c_void_p * n)(*[ptr(t["x"]) for t in layers])
+    iv = (ctypes.c_int * n)(*[t["x"].shape[-1] for t in layers])
+    hv = (ctypes.c_void_p * n)(*[ptr(t["h"]) for t in layers])
+    gv = (ctypes.c_void_p * (4 * n))(*[ptr(t[k]) for t in layers for k in ("dwih", "dwhh", "db1", "db2")])
+    av = (ctypes.c_int * n)(*[0] * n)
+    ws = layers[0]["ws"]
+    return lambda: call("vt_lstm16_bwd_weight_multi", n, ctypes.addressof(dv), ctypes.addressof(fv),
+                        ctypes.addressof(xv), ctypes.addressof(iv), ctypes.addressof(hv), B, S, H, ctypes.addressof(gv),
+                        ctypes.addressof(av), ptr(ws), ws.numel(), stream())
+
+
+if L16 and "vt_lstm16_bwd_weight_multi" in lib().fns:
+    In0, four = In, [a]
+    In = 64
+    four += [layer() for _ in range(3)]
+    In = In0
+    for t in four:
+        t["img"] = torch.randn(B, S, 4 * H, device=dev).bfloat16()
+    for name, ls, fmt in (("1 layer fp32 dG", [a], 0), ("1 layer bf16 image", [a], 1),
+                          (f"4 layers ({In}, 64, 64, 64) images", four, 1)):
+        us = timed(multi(ls, fmt))
+        print(f"In={In} bwd_weight_multi {name}: {us:7.1f} us per call, {us / len(ls):7.1f} us per layer", flush=True)

@@ -722,6 +722,62 @@ int vt_lstm_layer_bwd_weight(const float* dgates, const float* x, int In, const 
     return VT_OK;
 }
 
+// VAETEB_L16_DW16=0: the 16-bit LSTM's parameter gradients on the exact-fp32 kernel
+static bool l16_dw16_on() {
+    static const int dw16 = getenv("VAETEB_L16_DW16") ? atoi(getenv("VAETEB_L16_DW16")) : 1;
+    return dw16 != 0;
+}
+
+int vt_lstm16_dg16_ok(int In) { return l16_dw16_on() && In > 0 && In % 4 == 0 && In <= 64 ? 1 : 0; }
+
+int vt_lstm16_bwd_weight_multi(int nl, const void* const* dgates, const int* dg_bf16, const float* const* x,
+                               const int* In, const float* const* h, int B, int seq, int hidden, float* const* grads,
+                               const int* accumulate, float* ws, int64_t ws_floats, void* stream) {
+    VT_CHECK_ARG(hidden == H, "vt_lstm16_bwd_weight_multi: hidden size %d (kernel built for %d)", hidden, H);
+    VT_CHECK_ARG(nl >= 1 && nl <= SK_DW16_MAX_LAYERS, "vt_lstm16_bwd_weight_multi: %d layers (1 to %d)", nl,
+                 SK_DW16_MAX_LAYERS);
+    VT_CHECK_ARG(dgates && dg_bf16 && x && In && h && grads && accumulate && ws,
+                 "vt_lstm16_bwd_weight_multi: null pointer");
+    VT_CHECK_ARG(B > 0 && seq > 0 && (int64_t)B * seq < ((int64_t)1 << 31), "vt_lstm16_bwd_weight_multi: shape");
+    const int64_t R = (int64_t)B * seq;
+    Dw16Layer fast[SK_DW16_MAX_LAYERS];
+    int nf = 0, slow[SK_DW16_MAX_LAYERS], ns = 0;
+    for (int l = 0; l < nl; ++l) {
+        VT_CHECK_ARG(In[l] > 0 && In[l] + H + 1 <= SK_MAX_K1, "vt_lstm16_bwd_weight_multi: shape (layer %d: In %d)", l,
+                     In[l]);
+        VT_CHECK_ARG(dgates[l] && x[l] && h[l] && grads[4 * l] && grads[4 * l + 1] && grads[4 * l + 2],
+                     "vt_lstm16_bwd_weight_multi: null pointer (layer %d)", l);
+        // bf16 operands on bf16 MFMA (skdw16.hip, the 16-bit model's precision: dG / x / h rounded to
+        // bf16, fp32 accumulation); VAETEB_L16_DW16=0 or an unsupported shape: the exact-fp32 kernel,
+        // which reads fp32 dgates only
+        if (l16_dw16_on() && sk_lstm16_dw_ok(dgates[l], x[l], In[l], h[l])) {
+            Dw16Layer& L = fast[nf++];
+            L.dG = dgates[l], L.x = x[l], L.h = h[l];
+            L.dW_ih = grads[4 * l], L.dW_hh = grads[4 * l + 1], L.db_ih = grads[4 * l + 2], L.db_hh = grads[4 * l + 3];
+            L.part = nullptr;
+            L.In = In[l], L.fmt = dg_bf16[l] != 0, L.accumulate = accumulate[l];
+        } else {
+            VT_CHECK_ARG(!dg_bf16[l],
+                         "vt_lstm16_bwd_weight_multi: layer %d (In %d) needs fp32 dgates (vt_lstm16_dg16_ok)", l,
+                         In[l]);
+            slow[ns++] = l;
+        }
+    }
+    if (nf > 0) {
+        const int rc = sk_lstm16_dw_multi(nf, fast, seq, R, ws, ws_floats, S(stream));
+        VT_CHECK_ARG(rc == VT_OK, "vt_lstm16_bwd_weight_multi: workspace too small");
+    }
+    for (int i = 0; i < ns; ++i) {   // stream-ordered after the batch: the workspace is free again
+        const int l = slow[i];
+        const int rc = sk_linear_bwd_weight2(static_cast<const float*>(dgates[l]), R, G4, x[l], In[l], h[l], H,
+                                             grads[4 * l], grads[4 * l + 1], grads[4 * l + 2], grads[4 * l + 3],
+                                             accumulate[l], ws, ws_floats, S(stream), seq);
+        VT_CHECK_ARG(rc == VT_OK, "vt_lstm16_bwd_weight_multi: workspace too small");
+    }
+    VT_LAUNCH_CHECK("vt_lstm16_bwd_weight_multi");
+    return VT_OK;
+}
+
 int vt_lstm16_layer_bwd_weight(const float* dgates, const float* x, int In, const float* h, int B, int seq,
                                int hidden, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int accumulate,
                                float* ws, int64_t ws_floats, void* stream) {
@@ -730,11 +786,9 @@ int vt_lstm16_layer_bwd_weight(const float* dgates, const float* x, int In, cons
                  "vt_lstm16_layer_bwd_weight: shape (In %d)", In);
     VT_CHECK_ARG(dgates && x && h && dw_ih && dw_hh && db_ih, "vt_lstm16_layer_bwd_weight: null pointer");
     const int64_t R = (int64_t)B * seq;
-    // bf16 operands on bf16 MFMA (skdw16.hip, the 16-bit model's precision: dG / x / h rounded to
-    // bf16, fp32 accumulation); VAETEB_L16_DW16=0 or an unsupported shape: the exact-fp32 kernel
-    static const int dw16 = getenv("VAETEB_L16_DW16") ? atoi(getenv("VAETEB_L16_DW16")) : 1;
-    if (dw16 && sk_lstm16_dw(dgates, x, In, h, seq, R, dw_ih, dw_hh, db_ih, db_hh, accumulate, ws, ws_floats,
-                             S(stream)) == VT_OK) {
+    // one fp32-dG layer of vt_lstm16_bwd_weight_multi: the same kernel, row partition and bits
+    if (l16_dw16_on() && sk_lstm16_dw(dgates, x, In, h, seq, R, dw_ih, dw_hh, db_ih, db_hh, accumulate, ws, ws_floats,
+                                      S(stream)) == VT_OK) {
         VT_LAUNCH_CHECK("vt_lstm16_layer_bwd_weight");
         return VT_OK;
     }

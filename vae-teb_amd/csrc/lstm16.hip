@@ -25,7 +25,10 @@
 // reference scales fp16 gradients with GradScaler, bf16 needs no scale), dh_rec
 // = dg_{t+1} W_hh as 8 MFMAs per wave and step; dX = dG W_ih of a chunk as a
 // dense chunk GEMM from the chunk's bf16 dg image, one burst per chunk.
-// dgates are written in fp32 for the weight gradients (vt_lstm_layer_bwd_weight).
+// dgates go to the weight gradients (skdw16.hip) in fp32 by gate row from the per-layer kernel,
+// and from the pair / quad kernels either so or, on request per layer, as the chunk image's own
+// bf16 values [B S][4H] in its column order k' = 4 u + g (one 8-byte store per lane and step
+// instead of four strided 4-byte ones; half the bytes).
 #include <stdlib.h>
 
 #include "common.h"
@@ -744,7 +747,7 @@ template <int NS, int NTX, int ROLE, int CH = 0>
 __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, const float* __restrict__ gates,
                                           const float* __restrict__ cst, const float* __restrict__ whh,
                                           const float* __restrict__ wih, int In, int B, int S,
-                                          float* __restrict__ dgates, float* __restrict__ dx,
+                                          float* __restrict__ dgates, int d16, float* __restrict__ dx,
                                           __bf16 (*dgs)[TC][NS][DS], float (*dximg)[NS][TC][H],
                                           __bf16 (*wT)[DS], int tile = 0, unsigned* flags = nullptr,
                                           unsigned* err = nullptr) {
@@ -839,13 +842,20 @@ __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, cons
                 float v0, v1, v2, v3;
                 cell_bwd16(dh, gq.x, gq.y, gq.z, gq.w, ftanh(c1), c0, dc, v0, v1, v2, v3);
                 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                *reinterpret_cast<bf16x4*>(&dgs[cur][i][sl][4 * u]) = bf16x4{(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
+                const bf16x4 v16 = bf16x4{(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
+                *reinterpret_cast<bf16x4*>(&dgs[cur][i][sl][4 * u]) = v16;
                 if (wr) {
-                    float* o = dgates + (ob + t) * G4 + u;
-                    o[0] = v0;
-                    o[H] = v1;
-                    o[2 * H] = v2;
-                    o[3 * H] = v3;
+                    if (d16) {
+                        // the bf16 image [B S][4H], columns k' = 4 u + g as in dgs: the row's 512 B
+                        // in one 8-B store per lane (the values the MFMAs above read, bit for bit)
+                        *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(dgates) + (ob + t) * G4 + 4 * u) = v16;
+                    } else {
+                        float* o = dgates + (ob + t) * G4 + u;
+                        o[0] = v0;
+                        o[H] = v1;
+                        o[2 * H] = v2;
+                        o[3 * H] = v3;
+                    }
                 }
             }
             lds_barrier();
@@ -892,8 +902,8 @@ __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, cons
 }
 
 // dh_out [B, S, H] at layer l + 1's outputs; gatesU / cU from layer l + 1's forward, gatesL /
-// cL from layer l's; W_hh / W_ih of both; dgU / dgL [B, S, 4H] fp32; dx [B, S, InL] (layer l's
-// input gradient; may be null)
+// cL from layer l's; W_hh / W_ih of both; dgU / dgL [B, S, 4H] fp32, or the bf16 image where fmt's
+// bit is set (bit 0 dgL, bit 1 dgU); dx [B, S, InL] (layer l's input gradient; may be null)
 template <int NS, int NTXL>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd2(const float* __restrict__ dh_out,
                                                         const float* __restrict__ gatesU, const float* __restrict__ cU,
@@ -901,7 +911,7 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd2(const float* __restrict_
                                                         const float* __restrict__ gatesL, const float* __restrict__ cL,
                                                         const float* __restrict__ whhL, const float* __restrict__ wihL,
                                                         int InL, int B, int S, float* __restrict__ dgU,
-                                                        float* __restrict__ dgL, float* __restrict__ dx) {
+                                                        float* __restrict__ dgL, float* __restrict__ dx, int fmt) {
     __shared__ __attribute__((aligned(16))) __bf16 dgsU[2][TC][NS][DS];
     __shared__ __attribute__((aligned(16))) __bf16 dgsL[2][TC][NS][DS];
     __shared__ __attribute__((aligned(16))) float dximg[2][NS][TC][H];
@@ -913,16 +923,16 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd2(const float* __restrict_
     }
     lds_barrier();
     if (threadIdx.x < G4)
-        bwd2_role<NS, 4, 0>(dh_out, gatesU, cU, whhU, wihU, H, B, S, dgU, nullptr, dgsU, dximg, wTU);
+        bwd2_role<NS, 4, 0>(dh_out, gatesU, cU, whhU, wihU, H, B, S, dgU, fmt & 2, nullptr, dgsU, dximg, wTU);
     else
-        bwd2_role<NS, NTXL, 1>(nullptr, gatesL, cL, whhL, wihL, InL, B, S, dgL, dx, dgsL, dximg, wTL);
+        bwd2_role<NS, NTXL, 1>(nullptr, gatesL, cL, whhL, wihL, InL, B, S, dgL, fmt & 1, dx, dgsL, dximg, wTL);
 }
 
 // four layers' backward in one launch: workgroups [0, T) run layers 3, 2 of tile b (the producer:
 // layer 2's dX, the gradient at layer 1's outputs, published chunk by chunk into dmid [B, S, H]),
 // [T, 2T) layers 1, 0 of tile b - T (the consumer, reading dmid as each chunk's flag comes up).
-// p: [w_ih, w_hh] x 4 layers; gc: [gates, c] x 4 layers; dg[4]: dgates of each layer; dx: layer
-// 0's input gradient (may be null).  Per role the arithmetic of two k_lstm16_bwd2 launches.
+// p: [w_ih, w_hh] x 4 layers; gc: [gates, c] x 4 layers; dg[4]: dgates of each layer (fmt bit l:
+// layer l's as the bf16 image); dx: layer 0's input gradient (may be null).  Per role the arithmetic of two k_lstm16_bwd2 launches.
 struct QuadB {
     const float* w_ih[4];
     const float* w_hh[4];
@@ -933,7 +943,7 @@ struct QuadB {
 template <int NS, int NTXL>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd4(const float* __restrict__ dh_out, QuadB q, int In0, int B,
                                                         int S, int T, float* __restrict__ dmid, float* __restrict__ dx,
-                                                        unsigned slot0) {
+                                                        unsigned slot0, int fmt) {
     unsigned* flags = g_chain_flags + slot0;
     unsigned* err = g_chain_err;
     __shared__ __attribute__((aligned(16))) __bf16 dgsU[2][TC][NS][DS];
@@ -950,17 +960,17 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd4(const float* __restrict_
     const int tile = cons ? (int)blockIdx.x - T : (int)blockIdx.x;
     if (!cons) {
         if (threadIdx.x < G4)
-            bwd2_role<NS, 4, 0, 1>(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], H, B, S, q.dg[3], nullptr, dgsU,
+            bwd2_role<NS, 4, 0, 1>(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], H, B, S, q.dg[3], fmt & 8, nullptr, dgsU,
                                    dximg, wTU, tile, flags, err);
         else
-            bwd2_role<NS, 4, 1, 1>(nullptr, q.gates[2], q.c[2], q.w_hh[2], q.w_ih[2], H, B, S, q.dg[2], dmid, dgsL,
+            bwd2_role<NS, 4, 1, 1>(nullptr, q.gates[2], q.c[2], q.w_hh[2], q.w_ih[2], H, B, S, q.dg[2], fmt & 4, dmid, dgsL,
                                    dximg, wTL, tile, flags, err);
     } else {
         if (threadIdx.x < G4)
-            bwd2_role<NS, 4, 0, 2>(dmid, q.gates[1], q.c[1], q.w_hh[1], q.w_ih[1], H, B, S, q.dg[1], nullptr, dgsU,
+            bwd2_role<NS, 4, 0, 2>(dmid, q.gates[1], q.c[1], q.w_hh[1], q.w_ih[1], H, B, S, q.dg[1], fmt & 2, nullptr, dgsU,
                                    dximg, wTU, tile, flags, err);
         else
-            bwd2_role<NS, NTXL, 1, 2>(nullptr, q.gates[0], q.c[0], q.w_hh[0], q.w_ih[0], In0, B, S, q.dg[0], dx, dgsL,
+            bwd2_role<NS, NTXL, 1, 2>(nullptr, q.gates[0], q.c[0], q.w_hh[0], q.w_ih[0], In0, B, S, q.dg[0], fmt & 1, dx, dgsL,
                                       dximg, wTL, tile, flags, err);
     }
 }
@@ -1079,22 +1089,26 @@ int vt_lstm16_pair_fwd(const float* x, int In, const float* w_ih0, const float* 
 
 int vt_lstm16_pair_bwd(const float* dh_out, const float* gates1, const float* c1, const float* w_hh1,
                        const float* w_ih1, const float* gates0, const float* c0, const float* w_hh0,
-                       const float* w_ih0, int In0, int B, int seq, int hidden, float* dgates1, float* dgates0,
-                       float* dx, void* stream) {
+                       const float* w_ih0, int In0, int B, int seq, int hidden, void* dgates1, void* dgates0,
+                       float* dx, void* stream, int dg_bf16) {
     VT_CHECK_ARG(hidden == H, "vt_lstm16_pair_bwd: hidden size %d (kernel built for %d)", hidden, H);
     VT_CHECK_ARG(B > 0 && seq > 0 && In0 > 0 && In0 <= 64, "vt_lstm16_pair_bwd: shape (input size %d, at most 64)",
                  In0);
     VT_CHECK_ARG(dh_out && gates1 && c1 && w_hh1 && w_ih1 && gates0 && c0 && w_hh0 && (w_ih0 || !dx) && dgates1 &&
                      dgates0,
                  "vt_lstm16_pair_bwd: null pointer");
+    VT_CHECK_ARG((dg_bf16 & ~3) == 0 && !(((dg_bf16 & 1 ? (uintptr_t)dgates0 : 0) | (dg_bf16 & 2 ? (uintptr_t)dgates1 : 0)) & 7),
+                 "vt_lstm16_pair_bwd: dgates format %d (bit 0: dgates0, bit 1: dgates1; images 8-byte aligned)", dg_bf16);
+    float* dg1 = static_cast<float*>(dgates1);
+    float* dg0 = static_cast<float*>(dgates0);
     const dim3 grid((B + 1) / 2);
     hipStream_t st = vt::S(stream);
     if (In0 <= 32)
         hipLaunchKernelGGL((k_lstm16_bwd2<2, 2>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
-                           c0, w_hh0, w_ih0, In0, B, seq, dgates1, dgates0, dx);
+                           c0, w_hh0, w_ih0, In0, B, seq, dg1, dg0, dx, dg_bf16);
     else
         hipLaunchKernelGGL((k_lstm16_bwd2<2, 4>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
-                           c0, w_hh0, w_ih0, In0, B, seq, dgates1, dgates0, dx);
+                           c0, w_hh0, w_ih0, In0, B, seq, dg1, dg0, dx, dg_bf16);
     VT_LAUNCH_CHECK("vt_lstm16_pair_bwd");
     return VT_OK;
 }
@@ -1151,37 +1165,40 @@ int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B
 }
 
 int vt_lstm16_quad_bwd(const float* dh_out, const float* const* w, const float* const* gc, int In0, int B, int seq,
-                       int hidden, float* const* dg, float* dmid, float* dx, void* stream) {
+                       int hidden, void* const* dg, float* dmid, float* dx, void* stream, int dg_bf16) {
     VT_CHECK_ARG(hidden == H, "vt_lstm16_quad_bwd: hidden size %d (kernel built for %d)", hidden, H);
     VT_CHECK_ARG(B > 0 && seq > 0 && In0 > 0 && In0 <= 64, "vt_lstm16_quad_bwd: shape (input size %d, at most 64)",
                  In0);
     VT_CHECK_ARG(dh_out && w && gc && dg && dmid, "vt_lstm16_quad_bwd: null pointer");
+    VT_CHECK_ARG((dg_bf16 & ~15) == 0, "vt_lstm16_quad_bwd: dgates format %d (bit l: layer l)", dg_bf16);
     QuadB q;
     for (int l = 0; l < 4; ++l) {
         q.w_ih[l] = w[2 * l];
         q.w_hh[l] = w[2 * l + 1];
         q.gates[l] = gc[2 * l];
         q.c[l] = gc[2 * l + 1];
-        q.dg[l] = dg[l];
+        q.dg[l] = static_cast<float*>(dg[l]);
+        VT_CHECK_ARG(!((dg_bf16 >> l) & 1) || !((uintptr_t)dg[l] & 7),
+                     "vt_lstm16_quad_bwd: dgates image of layer %d not 8-byte aligned", l);
         VT_CHECK_ARG(q.w_hh[l] && q.gates[l] && q.c[l] && q.dg[l] && (q.w_ih[l] || (l == 0 && !dx)),
                      "vt_lstm16_quad_bwd: null pointer (layer %d)", l);
     }
     const int T = (B + 1) / 2;
     if (!l16_chain_ok(T, seq)) {
         int rc = vt_lstm16_pair_bwd(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], q.gates[2], q.c[2], q.w_hh[2],
-                                    q.w_ih[2], H, B, seq, H, q.dg[3], q.dg[2], dmid, stream);
+                                    q.w_ih[2], H, B, seq, H, q.dg[3], q.dg[2], dmid, stream, (dg_bf16 >> 2) & 3);
         if (rc) return rc;
         return vt_lstm16_pair_bwd(dmid, q.gates[1], q.c[1], q.w_hh[1], q.w_ih[1], q.gates[0], q.c[0], q.w_hh[0],
-                                  q.w_ih[0], In0, B, seq, H, q.dg[1], q.dg[0], dx, stream);
+                                  q.w_ih[0], In0, B, seq, H, q.dg[1], q.dg[0], dx, stream, dg_bf16 & 3);
     }
     hipStream_t st = vt::S(stream);
     const unsigned slot0 = vt::arrive_slots((unsigned)(T * ((seq + TC - 1) / TC)), st);
     if (In0 <= 32)
         hipLaunchKernelGGL((k_lstm16_bwd4<2, 2>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
-                           dx, slot0);
+                           dx, slot0, dg_bf16);
     else
         hipLaunchKernelGGL((k_lstm16_bwd4<2, 4>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
-                           dx, slot0);
+                           dx, slot0, dg_bf16);
     VT_LAUNCH_CHECK("vt_lstm16_quad_bwd");
     return VT_OK;
 }

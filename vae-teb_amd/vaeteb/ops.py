@@ -128,6 +128,19 @@ _L16_PAIR_NS = 4 if os.environ.get("VAETEB_L16_PAIR_NS") == "4" else 2
 # concurrent, chained chunk by chunk through per-chunk flags; bit-identical to the pair launches)
 LSTM_CHAIN_FWD = int(os.environ.get("VAETEB_L16_CHAIN_FWD", "1"))
 LSTM_CHAIN_BWD = int(os.environ.get("VAETEB_L16_CHAIN_BWD", "1"))
+# gate gradients of the pair / quad backward handed to the weight gradients as the recurrence's
+# own bf16 image (half the bytes; the same parameter gradients bit for bit); 0: fp32 dgates
+LSTM_DG16 = int(os.environ.get("VAETEB_L16_DG16", "1"))
+
+
+def _dg16(In):
+    """The layer's dgates as the bf16 image? (vt_lstm16_dg16_ok: the bf16 weight-gradient kernel
+    takes the layer; otherwise fp32 dgates for the exact-fp32 kernel)"""
+    return bool(LSTM_DG16 and _lib.lib().fns["vt_lstm16_dg16_ok"](In))
+
+
+def _dgates(fmt, B, S, H, device):
+    return torch.empty((B, S, 4 * H), dtype=torch.bfloat16 if fmt else torch.float32, device=device)
 
 
 def _l16_pair_fits(S):
@@ -1029,13 +1042,53 @@ class LSTMF(torch.autograd.Function):
         ws = WS.get(WS_LINEAR, gy.device, 1)
         gx = None
         deferred = []
+        batch = []   # 16-bit layers whose parameter gradients share one vt_lstm16_bwd_weight_multi call
 
-        def wgrad(l, dg, half):
+        def wgrad16_flush(final=False):
+            """the batched layers' parameter gradients in one call: at the end of the backward
+            when every one goes to an in-place sink and LSTM_GRAD_DEFER is set (then on the
+            weight-gradient side stream when there is one), else after their recurrence launch"""
+            if not batch:
+                return
+            direct = all(e[5].direct for e in batch)
+            if direct and LSTM_GRAD_DEFER and not final:
+                return
+            side = LSTM_GRAD_STREAM if direct else None
+            on_side = side is not None and side.cuda_stream != _lib.stream()
+            if on_side:
+                _lib.wait_for(side)
+            for i in range(0, len(batch), 4):
+                grp = batch[i: i + 4]
+                n = len(grp)
+                dv = (ctypes.c_void_p * n)(*[ptr(e[1]) for e in grp])
+                fv = (ctypes.c_int * n)(*[int(e[2]) for e in grp])
+                xv = (ctypes.c_void_p * n)(*[ptr(e[3]) for e in grp])
+                iv = (ctypes.c_int * n)(*[e[3].shape[-1] for e in grp])
+                hv = (ctypes.c_void_p * n)(*[ptr(e[4]) for e in grp])
+                gv = (ctypes.c_void_p * (4 * n))(*[ptr(t) for e in grp for t in e[5].out])
+                av = (ctypes.c_int * n)(*[e[5].acc for e in grp])
+                with torch.cuda.stream(side if on_side else torch.cuda.current_stream()):
+                    ws_b = WS.get(WS_LINEAR, gy.device, 1)
+                    call("vt_lstm16_bwd_weight_multi", n, ctypes.addressof(dv), ctypes.addressof(fv),
+                         ctypes.addressof(xv), ctypes.addressof(iv), ctypes.addressof(hv), B, S, H,
+                         ctypes.addressof(gv), ctypes.addressof(av), ptr(ws_b), ws_b.numel(), _st())
+            for l, dg, _, inp, hp, pg in batch:
+                if on_side:
+                    for t in (dg, inp, hp):
+                        t.record_stream(side)
+                grads[4 * l: 4 * l + 4] = pg.result()
+            batch.clear()
+
+        def wgrad(l, dg, half, fmt=False):
             """every parameter gradient of layer l from its dgates (in place / deferred / on the
             weight-gradient side stream, as configured)"""
             inp, hp = saved[4 * l], saved[4 * l + 1]
             w_ih, w_hh, b_ih, b_hh = params[4 * l: 4 * l + 4]
             In = inp.shape[-1]
+            if half and H == 64:
+                # batched: dg fp32, or (fmt) the recurrence's bf16 image
+                batch.append((l, dg, fmt, inp, hp, _ParamGrads([w_ih, w_hh, b_ih, b_hh], [True] * 4)))
+                return
             wfn = "vt_lstm16_layer_bwd_weight" if half else "vt_lstm_layer_bwd_weight"
             if (LSTM_FUSED or half) and In + H + 1 <= 144:
                 # every parameter gradient of the layer in one pass over dg
@@ -1094,7 +1147,8 @@ class LSTMF(torch.autograd.Function):
             # the four layers' backward in one launch: layer 2's dX (dmid, the gradient at layer
             # 1's outputs) handed to layers 1, 0 chunk by chunk (vt_lstm16_quad_bwd)
             In0 = saved[0].shape[-1]
-            dgs = [torch.empty((B, S, 4 * H), device=gy.device) for _ in range(4)]
+            fmts = [_dg16(saved[4 * k].shape[-1]) for k in range(4)]
+            dgs = [_dgates(f, B, S, H, gy.device) for f in fmts]
             dmid = torch.empty((B, S, H), device=gy.device)
             need_dx = ctx.needs_input_grad[0]
             gin = torch.empty((B, S, In0), device=gy.device) if need_dx else None
@@ -1102,9 +1156,11 @@ class LSTMF(torch.autograd.Function):
             gv = (ctypes.c_void_p * 8)(*[ptr(saved[4 * k + i]) for k in range(4) for i in (3, 2)])
             dv = (ctypes.c_void_p * 4)(*[ptr(t) for t in dgs])
             call("vt_lstm16_quad_bwd", ptr(dh), ctypes.addressof(wv), ctypes.addressof(gv), In0, B, S, H,
-                 ctypes.addressof(dv), ptr(dmid), ptr(gin) if need_dx else None, _st())
+                 ctypes.addressof(dv), ptr(dmid), ptr(gin) if need_dx else None, _st(),
+                 sum(int(f) << k for k, f in enumerate(fmts)))
             for k in (3, 2, 1, 0):
-                wgrad(k, dgs[k], True)
+                wgrad(k, dgs[k], True, fmts[k])
+            wgrad16_flush()
             if need_dx:
                 dh = gx = gin
             l = -1
@@ -1116,15 +1172,17 @@ class LSTMF(torch.autograd.Function):
                 inpL, _, cL, gatesL = saved[4 * lo: 4 * lo + 4]
                 _, _, cU, gatesU = saved[4 * l: 4 * l + 4]
                 InL = inpL.shape[-1]
-                dgU = torch.empty((B, S, 4 * H), device=gy.device)
-                dgL = torch.empty_like(dgU)
+                fU, fL = _dg16(H), _dg16(InL)
+                dgU = _dgates(fU, B, S, H, gy.device)
+                dgL = _dgates(fL, B, S, H, gy.device)
                 need_dx = lo > 0 or ctx.needs_input_grad[0]
                 gin = torch.empty((B, S, InL), device=gy.device) if need_dx else None
                 call("vt_lstm16_pair_bwd", ptr(dh), ptr(gatesU), ptr(cU), ptr(params[4 * l + 1]), ptr(params[4 * l]),
                      ptr(gatesL), ptr(cL), ptr(params[4 * lo + 1]), ptr(params[4 * lo]), InL, B, S, H, ptr(dgU),
-                     ptr(dgL), ptr(gin) if need_dx else None, _st())
-                wgrad(l, dgU, True)
-                wgrad(lo, dgL, True)
+                     ptr(dgL), ptr(gin) if need_dx else None, _st(), int(fL) | int(fU) << 1)
+                wgrad(l, dgU, True, fU)
+                wgrad(lo, dgL, True, fL)
+                wgrad16_flush()
                 if need_dx:
                     dh = gx = gin
                 l -= 2
@@ -1150,10 +1208,12 @@ class LSTMF(torch.autograd.Function):
                 if need_dx:
                     call("vt_linear_bwd_data", ptr(dg), B * S, 4 * H, ptr(w_ih), In, ptr(gin), 0, _st())
             wgrad(l, dg, half)
+            wgrad16_flush()
             if need_dx:
                 dh = gin
                 gx = gin
             l -= 1
+        wgrad16_flush(final=True)
         if deferred:
             # the layers' parameter gradients after the whole recurrence chain, on the
             # weight-gradient side stream when there is one (joined before the bucket
