@@ -223,6 +223,36 @@ int vt_modulus(const void* in, float* out, int64_t count, void* stream);
 int vt_modulus_bwd(const void* in, const float* mod, const float* grad, void* grad_in, int64_t count, void* stream);
 int vt_subsample_fourier(const void* in, void* out, int64_t rows, int n, int k, void* stream);
 int vt_pad_reflect(const float* in, float* out, int64_t rows, int N, int pad_left, int pad_right, void* stream);
+/* Backward of the cascade and of pad / subsample_fourier (scatter_bwd.hip): adjoints of the
+ * launches above with respect to the data operand, complex gradients as (d/d re, d/d im) --
+ * what torch autograd gives the reference's trailing-dim-2 tensors
+ * (ref/kymatio/kymatio/scattering1d/core/scattering1d.py:197-399 differentiated;
+ * modulus convention of ModulusStable, ref/kymatio/kymatio/backend/torch_backend.py:63-96):
+ * lowpass_bwd:  g (B, out_C, i1-i0) row ch[p] placed at [i0, i1) of a zero row of n/k,
+ *               gX = fft(.) / (n/k), gU[b,p,m + c n/k] = phi[m + c n/k] gX[m] / k;
+ * mod_spec_bwd: gX = fft(Re(unnormalised ifft(gUh)) z / |z|) / L (0 where |z| = 0), z
+ *               recomputed from A as vt_scat_mod_spec does; L = n/k <= 4096 (three LDS
+ *               images), longer rows are composed from filter_sub, vt_fft / vt_fft_large and
+ *               modulus_cplx_bwd;
+ * fold_bwd:     gA[b,a,i] = (1/k) sum_{q in [csr_ptr[a], csr_ptr[a+1])} pool[f_off[p] + i] *
+ *               gX[b, p, i mod n/k], p = csr_p[q] (the filters whose a_idx is a, in fixed
+ *               order; no atomics, bitwise reproducible), i < n;
+ * modulus_cplx_bwd: out = Re(G) z / |z| (0 where |z| = 0);
+ * pad_reflect_bwd: gx[i] = scale * (g[pl+i] + g[pl-i] (1 <= i <= pl) + g[pl+2N-2-i]
+ *               (N-1-pr <= i <= N-2)), pads < N; g elements g_stride floats apart (2 reads
+ *               the real part of a complex row);
+ * subsample_fourier_bwd: gx[r, m + c n/k] = g[r, m] / k.                                  */
+int vt_scat_lowpass_bwd(const float* g, int B, int P, int n, const float* phi, int k, int i0, int i1, const int* ch,
+                        int out_C, const void* tw, void* gU, void* stream);
+int vt_scat_mod_spec_bwd(const void* A, int B, int64_t a_rows, int n, const int* a_idx, const float* pool,
+                         const int64_t* f_off, int P, int k, const void* tw, const void* gUh, void* gX,
+                         void* stream);
+int vt_scat_fold_bwd(const void* gX, int B, int a_rows, int n, const int* csr_ptr, const int* csr_p,
+                     const float* pool, const int64_t* f_off, int P, int k, void* gA, void* stream);
+int vt_modulus_cplx_bwd(const void* z, const void* G, void* out, int64_t count, void* stream);
+int vt_pad_reflect_bwd(const float* g, int g_stride, float scale, float* gx, int64_t rows, int N, int pad_left,
+                       int pad_right, void* stream);
+int vt_subsample_fourier_bwd(const void* g, void* gx, int64_t rows, int n, int k, void* stream);
 
 
 /* ---------------------------------------------------------------------- ELBO

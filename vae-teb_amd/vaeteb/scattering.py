@@ -16,12 +16,19 @@ Two entry points mirror the reference's plugin API:
   oversampling-0 case (the one the VAE-TEB front-end uses) runs the fused
   kernels of vaeteb.frontend; everything else runs the generic scattering
   core below over the HIP backend plugin.
+
+Both are differentiable in the input, once, like the reference's torch
+frontend under autograd: every plugin op and every launch group of the batched
+cascade is an autograd.Function whose backward is the adjoint HIP kernel
+(csrc/scatter_bwd.hip).  Filters are constants.  With no input requiring grad
+every op launches exactly what the forward-only code launched.
 """
 import math
 
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .filter_bank import build_bank, padding, twiddles
@@ -55,6 +62,99 @@ class _ModulusStable(torch.autograd.Function):
         _lib.call("vt_modulus_bwd", _lib.ptr(x), _lib.ptr(out), _lib.ptr(g.contiguous()), _lib.ptr(gi), out.numel(),
                   _lib.stream())
         return gi
+
+
+def _needs_grad(x):
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+def _fft_adjoint(g, inverse):
+    """Adjoint of _fft(., inverse): of fft the unnormalised inverse, of ifft (1/n) fft / n --
+    vt_fft / vt_fft_large with the other flag, times a power of two (exact)."""
+    n = g.shape[-2]
+    return TorchHipBackend1D._fft(g.contiguous(), not inverse).mul_(1.0 / n if inverse else float(n))
+
+
+class _FFT(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, inverse):
+        ctx.inverse = inverse
+        return TorchHipBackend1D._fft(x, inverse)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _fft_adjoint(g, ctx.inverse), None
+
+
+class _RFFT(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return TorchHipBackend1D._rfft(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _fft_adjoint(g, False)[..., :1].contiguous()     # the adjoint keeps the real part
+
+
+class _IRFFT(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return TorchHipBackend1D._irfft(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gc = torch.zeros(g.shape[:-1] + (2,), dtype=g.dtype, device=g.device)   # the adjoint embeds the real part
+        gc[..., 0] = g[..., 0]
+        return _fft_adjoint(gc, True)
+
+
+class _Cdgmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B):
+        # gA = gC . conj(B): vt_cdgmm with the conjugated filter (a constant, conjugated once here)
+        ctx.Bc = B if B.shape[-1] == 1 else (B * B.new_tensor([1.0, -1.0])).contiguous()
+        return TorchHipBackend1D._cdgmm(A, B)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return TorchHipBackend1D._cdgmm(g.contiguous(), ctx.Bc), None
+
+
+class _SubsampleFourier(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k):
+        ctx.k = k
+        return TorchHipBackend1D._subsample_fourier(x, k)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        L, k = g.shape[-2], ctx.k
+        gx = torch.empty(g.shape[:-2] + (L * k, 2), dtype=g.dtype, device=g.device)
+        _lib.call("vt_subsample_fourier_bwd", _lib.ptr(g), _lib.ptr(gx), g.numel() // (2 * L), L * k, k, _lib.stream())
+        return gx, None
+
+
+class _PadReflect(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pad_left, pad_right):
+        ctx.pads, ctx.shape = (pad_left, pad_right), x.shape
+        return TorchHipBackend1D._pad(x, pad_left, pad_right)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        N = ctx.shape[-1]
+        gx = torch.empty(ctx.shape, dtype=g.dtype, device=g.device)
+        _lib.call("vt_pad_reflect_bwd", _lib.ptr(g), 1, 1.0, _lib.ptr(gx), gx.numel() // N, N, ctx.pads[0],
+                  ctx.pads[1], _lib.stream())
+        return gx, None, None
 
 
 class TorchHipBackend1D:
@@ -130,6 +230,13 @@ class TorchHipBackend1D:
         if not B.is_cuda and A.is_cuda:
             raise TypeError("Input must be on CPU.")
         cls._device_check(A)
+        if B.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("torch_hip backend: cdgmm is not differentiable in the filter B "
+                               "(filters are constants; detach B)")
+        return _Cdgmm.apply(A, B) if _needs_grad(A) else cls._cdgmm(A, B)
+
+    @classmethod
+    def _cdgmm(cls, A, B):
         n = B.numel() // B.shape[-1]
         C = torch.empty_like(A)
         _lib.call("vt_cdgmm", _lib.ptr(A), _lib.ptr(B), int(cls._is_real(B)), _lib.ptr(C), A.numel() // (2 * n), n,
@@ -140,6 +247,10 @@ class TorchHipBackend1D:
     def subsample_fourier(cls, x, k):
         cls.complex_check(x)
         cls._device_check(x)
+        return _SubsampleFourier.apply(x, k) if _needs_grad(x) else cls._subsample_fourier(x, k)
+
+    @staticmethod
+    def _subsample_fourier(x, k):
         x = x.contiguous()
         N = x.shape[-2]
         out = torch.empty(x.shape[:-2] + (N // k, 2), dtype=x.dtype, device=x.device)
@@ -150,11 +261,17 @@ class TorchHipBackend1D:
     def pad(x, pad_left, pad_right):
         if (pad_left >= x.shape[-1]) or (pad_right >= x.shape[-1]):
             raise ValueError("Indefinite padding size (larger than tensor).")
+        out = _PadReflect.apply(x, pad_left, pad_right) if _needs_grad(x) else TorchHipBackend1D._pad(x, pad_left,
+                                                                                                      pad_right)
+        return out[..., None]
+
+    @staticmethod
+    def _pad(x, pad_left, pad_right):
         x = x.contiguous()
         N = x.shape[-1]
         out = torch.empty(x.shape[:-1] + (N + pad_left + pad_right,), dtype=x.dtype, device=x.device)
         _lib.call("vt_pad_reflect", _lib.ptr(x), _lib.ptr(out), x.numel() // N, N, pad_left, pad_right, _lib.stream())
-        return out[..., None]
+        return out
 
     @staticmethod
     def unpad(x, i0, i1):
@@ -182,6 +299,10 @@ class TorchHipBackend1D:
     def rfft(cls, x):
         cls.contiguous_check(x)
         cls.real_check(x)
+        return _RFFT.apply(x) if _needs_grad(x) else cls._rfft(x)
+
+    @classmethod
+    def _rfft(cls, x):
         x_r = torch.zeros(x.shape[:-1] + (2,), dtype=x.dtype, device=x.device)
         x_r[..., 0] = x[..., 0]
         return cls._fft(x_r, False)
@@ -190,19 +311,23 @@ class TorchHipBackend1D:
     def irfft(cls, x):
         cls.contiguous_check(x)
         cls.complex_check(x)
+        return _IRFFT.apply(x) if _needs_grad(x) else cls._irfft(x)
+
+    @classmethod
+    def _irfft(cls, x):
         return cls._fft(x, True)[..., :1].contiguous()
 
     @classmethod
     def ifft(cls, x):
         cls.contiguous_check(x)
         cls.complex_check(x)
-        return cls._fft(x, True)
+        return _FFT.apply(x, True) if _needs_grad(x) else cls._fft(x, True)
 
     @classmethod
     def fft(cls, x):
         cls.contiguous_check(x)
         cls.complex_check(x)
-        return cls._fft(x, False)
+        return _FFT.apply(x, False) if _needs_grad(x) else cls._fft(x, False)
 
     @staticmethod
     def multiply(x, y):
@@ -281,6 +406,69 @@ def scattering1d_core(x, bk, J, T, psi1, psi2, phi, pad_left, pad_right, ind_sta
 
 
 # ------------------------------------------------------------- batched cascade
+_BWD_MAX_LDS = 4096     # vt_scat_mod_spec_bwd keeps three LDS images of a row; longer rows are composed
+
+
+class _CascadeTop(torch.autograd.Function):
+    """U0^ = fft(pad(x)); backward gx = pad_bwd(Re(unnormalised ifft(gU0^)))."""
+
+    @staticmethod
+    def forward(ctx, x2, cas):
+        ctx.cas, ctx.shape = cas, x2.shape
+        return cas._top(x2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        cas, (B, N) = ctx.cas, ctx.shape
+        G = TorchHipBackend1D._fft(g.contiguous(), True)      # (1/n) ifft; the n goes into the pad's adjoint
+        gx = torch.empty((B, N), device=cas.dev)
+        _lib.call("vt_pad_reflect_bwd", _lib.ptr(G), 2, float(cas.n), _lib.ptr(gx), B, N, cas.pad[0], cas.pad[1],
+                  _lib.stream())
+        return gx, None
+
+
+class _CascadeSpectrum(torch.autograd.Function):
+    """_Cascade._spectrum of one level; backward vt_scat_mod_spec_bwd (or its composed
+    form for long rows) then vt_scat_fold_bwd.  Saves A only: z is recomputed."""
+
+    @staticmethod
+    def forward(ctx, A, cas, a_rows, n_in, g):
+        ctx.cas, ctx.meta = cas, (a_rows, n_in, g)
+        ctx.save_for_backward(A)
+        return cas._spectrum(A, A.shape[0], a_rows, n_in, g)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gUh):
+        (A,), cas, (a_rows, n_in, g) = ctx.saved_tensors, ctx.cas, ctx.meta
+        return cas._spectrum_bwd(A, gUh.contiguous(), a_rows, n_in, g), None, None, None, None
+
+
+class _CascadeLowpass(torch.autograd.Function):
+    """_Cascade._lowpass writing its channels of `out` in place; backward
+    vt_scat_lowpass_bwd.  The gradient of `out` passes through to the launches
+    that filled its other channels."""
+
+    @staticmethod
+    def forward(ctx, U, out, cas, P, L, spec):
+        ctx.cas, ctx.meta, ctx.ushape = cas, (U.shape[0], P, L, spec), U.shape
+        cas._lowpass(U, U.shape[0], P, L, spec, out)
+        ctx.mark_dirty(out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        cas, (B, P, L, spec) = ctx.cas, ctx.meta
+        g = g.contiguous()
+        foff, k, i0, i1, ch = spec
+        gU = torch.empty(ctx.ushape, device=cas.dev)
+        _lib.call("vt_scat_lowpass_bwd", _lib.ptr(g), B, P, L, cas.pool.data_ptr() + 4 * foff, k, i0, i1,
+                  _lib.ptr(ch), cas.C, _lib.ptr(_tw(L // k, cas.dev)), _lib.ptr(gU), _lib.stream())
+        return gU, g, None, None, None, None
+
+
 class _Cascade:
     """The cascade of scattering1d_core (orders 1-2, average=True, array output)
     regrouped by subsampling level: every (sample, filter) row of a level is one
@@ -288,7 +476,12 @@ class _Cascade:
     modulus -> rfft in LDS) and vt_scat_lowpass (phi, subsample, irfft, unpad ->
     its output channel).  Same arithmetic and channel order as the reference
     loop (ref/kymatio/kymatio/scattering1d/core/scattering1d.py:197-399); ~3
-    launches per level instead of ~6 per filter and per filter pair."""
+    launches per level instead of ~6 per filter and per filter pair.
+
+    Differentiable in x: under autograd every launch group is an
+    autograd.Function (_CascadeTop, _CascadeSpectrum, _CascadeLowpass) whose
+    backward is the adjoint kernel of csrc/scatter_bwd.hip; autograd sums the
+    gradients that the levels send into U0^ and U1^."""
 
     def __init__(self, sc, device):
         b, J, os_ = sc._bank, sc.J, sc.oversampling
@@ -347,6 +540,13 @@ class _Cascade:
             self.levels.append(lvl)
         self.pool = torch.from_numpy(np.concatenate(pool)).to(device)
         self.pad = (sc.pad_left, sc.pad_right)
+        # inverse of a_idx for vt_scat_fold_bwd: the filters of each parent row, in filter order (CSR)
+        for lvl in self.levels:
+            for g, a_rows in [(lvl, 1)] + [(sg, lvl["P"]) for sg in lvl["sub"]]:
+                a_idx = g["a_idx"].tolist()
+                kids = [[p for p, a in enumerate(a_idx) if a == r] for r in range(a_rows)]
+                g["csr_ptr"] = i32(np.cumsum([0] + [len(c) for c in kids]).tolist())
+                g["csr_p"] = i32([p for c in kids for p in c])
 
     def _spectrum(self, A, B, a_rows, n_in, g):
         """U^ = rfft(|ifft(subsample(A[a_idx] . psi, k))|) for every (b, p) row of
@@ -366,6 +566,26 @@ class _Cascade:
         _lib.call("vt_fft_large", _lib.ptr(Y), _lib.ptr(out), _lib.ptr(ws), rows, L, 0, tw, _lib.stream())
         return out
 
+    def _spectrum_bwd(self, A, gUh, a_rows, n_in, g):
+        """Adjoint of _spectrum with respect to A: gX (B, P, L, 2) from gU^, then the
+        fold's adjoint summed over the filters of each parent row -> gA like A."""
+        B, L, P = A.shape[0], g["L"], g["P"]
+        tw = _lib.ptr(_tw(L, self.dev))
+        if L <= _BWD_MAX_LDS:
+            gX = torch.empty((B, P, L, 2), device=self.dev)
+            _lib.call("vt_scat_mod_spec_bwd", _lib.ptr(A), B, a_rows, n_in, _lib.ptr(g["a_idx"]), _lib.ptr(self.pool),
+                      _lib.ptr(g["f_off"]), P, g["k"], tw, _lib.ptr(gUh), _lib.ptr(gX), _lib.stream())
+        else:
+            # z = ifft(fold(A)) and G = ifft(gU^), both with 1/L: gX = fft(Re(L G) z / |z|) / L = fft(Re(G) z / |z|)
+            z = TorchHipBackend1D._fft(self._filter_sub(A, B, a_rows, n_in, g), True)
+            G = TorchHipBackend1D._fft(gUh, True)
+            _lib.call("vt_modulus_cplx_bwd", _lib.ptr(z), _lib.ptr(G), _lib.ptr(G), B * P * L, _lib.stream())
+            gX = TorchHipBackend1D._fft(G, False)
+        gA = torch.empty_like(A)
+        _lib.call("vt_scat_fold_bwd", _lib.ptr(gX), B, a_rows, n_in, _lib.ptr(g["csr_ptr"]), _lib.ptr(g["csr_p"]),
+                  _lib.ptr(self.pool), _lib.ptr(g["f_off"]), P, g["k"], _lib.ptr(gA), _lib.stream())
+        return gA
+
     def _lowpass(self, U, B, P, L, spec, out):
         foff, k, i0, i1, ch = spec
         _lib.call("vt_scat_lowpass", _lib.ptr(U), B, P, L, self.pool.data_ptr() + 4 * foff, k, i0, i1, _lib.ptr(ch),
@@ -379,13 +599,10 @@ class _Cascade:
 
     def __call__(self, x2):
         """x2 (B, N) float32 contiguous on device -> S (B, C, S_out)."""
-        B, N = x2.shape
-        n = self.n
-        xp = torch.empty((B, n), device=self.dev)
-        _lib.call("vt_pad_reflect", _lib.ptr(x2), _lib.ptr(xp), B, N, self.pad[0], self.pad[1], _lib.stream())
-        xc = torch.zeros((B, n, 2), device=self.dev)
-        xc[..., 0] = xp
-        U0h = TorchHipBackend1D._fft(xc, False)
+        if _needs_grad(x2):
+            return self._call_grad(x2)
+        B, n = x2.shape[0], self.n
+        U0h = self._top(x2)
         out = torch.empty((B, self.C, self.S), device=self.dev)
         self._lowpass(U0h, B, 1, n, self.s0, out)
         for lvl in self.levels:
@@ -394,6 +611,29 @@ class _Cascade:
             for g in lvl["sub"]:
                 U2h = self._spectrum(U1h, B, lvl["P"], lvl["L"], g)
                 self._lowpass(U2h, B, g["P"], g["L"], g["s2"], out)
+        return out
+
+    def _top(self, x2):
+        B, N = x2.shape
+        n = self.n
+        xp = torch.empty((B, n), device=self.dev)
+        _lib.call("vt_pad_reflect", _lib.ptr(x2), _lib.ptr(xp), B, N, self.pad[0], self.pad[1], _lib.stream())
+        xc = torch.zeros((B, n, 2), device=self.dev)
+        xc[..., 0] = xp
+        return TorchHipBackend1D._fft(xc, False)
+
+    def _call_grad(self, x2):
+        """__call__ under autograd: the same launches in the same order, each group an autograd.Function."""
+        B, n = x2.shape[0], self.n
+        U0h = _CascadeTop.apply(x2, self)
+        out = torch.empty((B, self.C, self.S), device=self.dev)
+        out = _CascadeLowpass.apply(U0h, out, self, 1, n, self.s0)
+        for lvl in self.levels:
+            U1h = _CascadeSpectrum.apply(U0h, self, 1, n, lvl)
+            out = _CascadeLowpass.apply(U1h, out, self, lvl["P"], lvl["L"], lvl["s1"])
+            for g in lvl["sub"]:
+                U2h = _CascadeSpectrum.apply(U1h, self, lvl["P"], lvl["L"], g)
+                out = _CascadeLowpass.apply(U2h, out, self, g["P"], g["L"], g["s2"])
         return out
 
 
@@ -450,10 +690,11 @@ class Scattering1D(nn.Module):
                 and self.out_type == "array" and 2 ** self.J_pad <= 8192)
 
     def _cascade_ok(self, x):
-        """Batched level-grouped cascade: average=True, array output, no autograd
-        (the generic core over the plugin keeps the reference's autograd)."""
+        """Batched level-grouped cascade: average=True, array output, orders 1-2, with
+        or without autograd (its backward is csrc/scatter_bwd.hip).  Everything else
+        runs the generic core over the plugin, whose ops are autograd.Functions."""
         return (self.cascade and self.average and self.out_type == "array" and self.vectorize and self.max_order in (1, 2)
-                and not (torch.is_grad_enabled() and x.requires_grad) and x.is_cuda)
+                and x.is_cuda)
 
     def meta(self):
         raise NotImplementedError("meta() is outside the training path")
@@ -468,7 +709,7 @@ class Scattering1D(nn.Module):
                              "Please set out_type to 'list' or vectorize to False.")
         batch_shape = x.shape[:-1]
         x2 = x.reshape((-1, x.shape[-1])).contiguous()
-        if self._fused_ok():
+        if self._fused_ok() and not _needs_grad(x2):   # the fused first-order kernels have no backward
             S = self._fused_forward(x2)
         elif self._cascade_ok(x2):
             if self._cascade is None or self._cascade.dev != x2.device:
