@@ -76,6 +76,14 @@ int vt_get_h16_format(void);
  *           _pad_signal + fft ref/hdf5_dataset/kymatio_phase_scattering.py:162-205,222-223 */
 int vt_fe_spectrum(const float* x, int64_t rows, int N, int n_pad, int pad_left, int pad_mode, const void* tw,
                    void* xhat, void* stream);
+/* The same for every (row b, shift k): xhat[b*K + k] = padded spectrum of np.roll(x[b], shifts[k]),
+ * read in place as x[b*x_row_stride + ((pad_src(n - pad_left) - shifts[k]) mod N)] (no rolled copies;
+ * shifts: device int[K], any sign and magnitude; x_row_stride lets channel 1 of a (B, 2, N) batch be
+ * read where it lies).  Same values into the same FFT as vt_fe_spectrum on the rolled row.
+ * replaces: np.roll(signal, shift) + the front-end's pad + fft, once per shift
+ *           ref/model/graph_model.py:1443-1458 (_apply_circular_shift), :1322-1339                */
+int vt_fe_spectrum_rolled(const float* x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left,
+                          int pad_mode, const int* shifts, int K, const void* tw, void* xhat, void* stream);
 
 /* S0: phi-lowpass + 2^log2T decimation of the padded signal, as a short
  * correlation with h0 = ifft(phi_0) (even, radius taps each side).
@@ -106,6 +114,17 @@ int vt_fe_wavelet(const void* xhat, int64_t B, int C, int n_pad, const float* ps
 int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, int pad_left, int n_pairs,
                 const int* slot_i, const int* slot_j, const float* power, const void* tw, const float* phi0, int dec,
                 int start, int S, int pad_mode, float* out, void* stream);
+/* vt_fe_pairs with the two operands in different buffers, for B*K rows r: a_i =
+ * analytic_i[(r / K)*n_slots_i + slot_i[p]] (one set per recording: the fhr signals a front-end
+ * call left behind), a_j = analytic_j[r*n_slots_j + slot_j[p]] (one set per (recording, shift):
+ * the rolled up channel); out (B*K, n_pairs, S).  Each row's arithmetic is vt_fe_pairs's on the
+ * same two signals (same kernel family for the geometry and settings: the same bits).
+ * replaces: the cross-phase front-end call re-run per shift, ref/model/graph_model.py:1322-1339
+ *           (_compute_cross_channel_phase_correlation, kymatio_phase_scattering.py:303-360)       */
+int vt_fe_pairs_split(const void* analytic_i, int n_slots_i, const void* analytic_j, int n_slots_j, int64_t B, int K,
+                      int N, int n_pad, int pad_left, int n_pairs, const int* slot_i, const int* slot_j,
+                      const float* power, const void* tw, const float* phi0, int dec, int start, int S,
+                      int pad_mode, float* out, void* stream);
 
 /* Product staging of vt_fe_pairs on the training geometry (N 4096, n_pad 8192, dec 16):
  * 0 = the product is formed once per sample into LDS (default), 1 = each thread forms
@@ -280,6 +299,15 @@ int vt_elbo_output_fwd(const float* mu, const float* lv, const float* y, int64_t
                        float* g_lv, float* g_lin, float* nll, float* mse, float* ws, void* stream);
 /* x *= s[0] (s a device scalar): applies an upstream loss gradient.             */
 int vt_scale_by_device_scalar(float* x, int64_t n, const float* s, void* stream);
+/* Transfer entropy of B*K (recording, shift) rows r of row_elems = S*L values each: posterior pieces
+ * mu_c, lv_q (B*K, S, L); prior mu_y, lv_p (B, S, L) read at row r / K.  te[r] = mean over the row of
+ * 0.5*(lv_p - lv_q - 1 + (exp(lv_q) + (mu_c + mu_y - mu_y)^2)/exp(lv_p)) (vt_elbo_latent_fwd's
+ * expression and order); kl (nullable): the elementwise values (B*K, S, L).  One workgroup per row,
+ * fixed-order sum in double, no atomics: identical run to run and under any split of the rows.
+ * replaces: measure_transfer_entropy(reduce_mean=False) ref/model/vae_teb_model.py:1194-1226 +
+ *           kld_tensor.mean() ref/model/graph_model.py:1371, once per shift                       */
+int vt_te_kl_rows(const float* mu_c, const float* lv_q, const float* mu_y, const float* lv_p, int64_t B, int K,
+                  int64_t row_elems, float* te, float* kl, void* stream);
 
 /* ----------------------------------------------------------------- optimiser
  * Flat fp32 buffers: every parameter / gradient / moment is a view of one

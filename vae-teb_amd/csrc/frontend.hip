@@ -10,6 +10,9 @@
 //   vt_fe_pairs     one workgroup per (sample, selected pair): accelerated
 //                   product, reflect-pad, FFT, x phi, crop, 512-pt iFFT, real
 //   vt_fe_normalize log/asinh + per-channel z-score, (B,C,S) -> (B,S,C)
+// The transfer-entropy shift sweep (vaeteb/te.py) adds two forms over B x K (recording, shift) rows:
+//   vt_fe_spectrum_rolled  vt_fe_spectrum of the up channel rolled by each shift (a gather)
+//   vt_fe_pairs_split      vt_fe_pairs with the fhr operand per recording, the up operand per row
 // Reference: ref/kymatio/kymatio/scattering1d/core/scattering1d.py:197-399,
 // ref/hdf5_dataset/kymatio_phase_scattering.py:211-301 (+ :303-360 cross),
 // ref/hdf5_dataset/hdf5_dataset.py:18-137 (normalisation).
@@ -50,6 +53,34 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_spectrum(const float* __restr
     for (int n = threadIdx.x; n < n_pad; n += blockDim.x) {
         const int s = pad_src(n - pad_left, N, pad_mode);
         X[n] = make_float2(s < 0 ? 0.f : xr[s], 0.f);
+    }
+    __syncthreads();
+    float2* R = fft_lds<false>(X, Y, n_pad, tw, 1);
+    float2* o = xhat + row * n_pad;
+    for (int n = threadIdx.x; n < n_pad; n += blockDim.x) o[n] = R[n];
+}
+
+// k_fe_spectrum of np.roll(x[b], shifts[k]) for every (b, k), row b * K + k of xhat, without the
+// rolled copies: padded position n reads x[b][(pad_src(n - pad_left) - shift_k) mod N] (the roll
+// comes before the padding, ref/model/graph_model.py:1443-1458, so each shift is its own FFT).
+// The values entering the FFT are those of k_fe_spectrum on the rolled row: the same bits.
+__global__ __launch_bounds__(FE_THREADS) void k_fe_spectrum_rolled(const float* __restrict__ x, int64_t x_row_stride,
+                                                                   int N, int n_pad, int pad_left, int pad_mode,
+                                                                   const int* __restrict__ shifts, int K,
+                                                                   const float2* __restrict__ tw,
+                                                                   float2* __restrict__ xhat) {
+    extern __shared__ __attribute__((aligned(16))) float2 sm[];
+    float2* X = sm;
+    float2* Y = sm + n_pad;
+    const int64_t row = blockIdx.x;
+    const float* xr = x + (row / K) * x_row_stride;
+    int sh = shifts[row % K] % N;   // any sign, any magnitude -> [0, N)
+    if (sh < 0) sh += N;
+    for (int n = threadIdx.x; n < n_pad; n += blockDim.x) {
+        const int s = pad_src(n - pad_left, N, pad_mode);
+        int q = s - sh;             // s in [0, N): q in (-N, N)
+        if (q < 0) q += N;
+        X[n] = make_float2(s < 0 ? 0.f : xr[q], 0.f);
     }
     __syncthreads();
     float2* R = fft_lds<false>(X, Y, n_pad, tw, 1);
@@ -206,21 +237,16 @@ __device__ __forceinline__ float2 pair_polar(float2 pi, float2 pj, float p) {
     const float m = pi.y * pj.y;
     return make_float2(m * __builtin_amdgcn_cosf(v), m * __builtin_amdgcn_sinf(v));
 }
+// The body of one (row, pair) item: ai / aj are the item's two analytic signals (N samples each)
+// and o its output row.  k_fe_pairs takes both from one buffer, k_fe_pairs_split from two.
 template <bool POLAR>
-__global__ __launch_bounds__(FE_THREADS) void k_fe_pairs(
-    const float2* __restrict__ analytic, int n_slots, int N, int n_pad, int pad_left, int n_pairs,
-    const int* __restrict__ slot_i, const int* __restrict__ slot_j, const float* __restrict__ power,
-    const float2* __restrict__ tw, const float* __restrict__ phi0, int dec, int start, int S, int pad_mode,
-    float* __restrict__ out) {
+__device__ __forceinline__ void fe_pairs_item(const float2* ai, const float2* aj, float* __restrict__ o, const float pw,
+                                              int N, int n_pad, int pad_left, const float2* __restrict__ tw,
+                                              const float* __restrict__ phi0, int dec, int start, int S,
+                                              int pad_mode) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     float2* X = sm;
     float2* Y = sm + n_pad;
-    const int pair = blockIdx.x;
-    const int64_t b = blockIdx.y;
-    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
-    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
-    const float pw = power[pair];
-    float* o = out + (b * n_pairs + pair) * (int64_t)S;
     // accelerated product (kymatio_phase_scattering.py:211-218, :282-283)
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
         const float2 u = ai[i], v = aj[i];
@@ -251,6 +277,39 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_pairs(
     float2* Rs = fft_lds<true>(Z, R, nb, tw, dec);
     const float inv = 1.0f / (float)nb;
     for (int m = threadIdx.x; m < S; m += blockDim.x) o[m] = Rs[start + m].x * inv;
+}
+
+template <bool POLAR>
+__global__ __launch_bounds__(FE_THREADS) void k_fe_pairs(
+    const float2* __restrict__ analytic, int n_slots, int N, int n_pad, int pad_left, int n_pairs,
+    const int* __restrict__ slot_i, const int* __restrict__ slot_j, const float* __restrict__ power,
+    const float2* __restrict__ tw, const float* __restrict__ phi0, int dec, int start, int S, int pad_mode,
+    float* __restrict__ out) {
+    const int pair = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    float* o = out + (b * n_pairs + pair) * (int64_t)S;
+    fe_pairs_item<POLAR>(ai, aj, o, pw, N, n_pad, pad_left, tw, phi0, dec, start, S, pad_mode);
+}
+
+// Split sources (the transfer-entropy shift sweep, vaeteb/te.py): row r = blockIdx.y of B * K takes
+// its i operand from the per-recording set analytic_i[r / K] and its j operand from the per-row set
+// analytic_j[r].  The item itself is k_fe_pairs's.
+template <bool POLAR>
+__global__ __launch_bounds__(FE_THREADS) void k_fe_pairs_split(
+    const float2* __restrict__ analytic_i, int n_slots_i, const float2* __restrict__ analytic_j, int n_slots_j, int K,
+    int N, int n_pad, int pad_left, int n_pairs, const int* __restrict__ slot_i, const int* __restrict__ slot_j,
+    const float* __restrict__ power, const float2* __restrict__ tw, const float* __restrict__ phi0, int dec,
+    int start, int S, int pad_mode, float* __restrict__ out) {
+    const int pair = blockIdx.x;
+    const int64_t r = blockIdx.y;
+    const float2* ai = analytic_i + ((r / K) * n_slots_i + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic_j + (r * n_slots_j + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    float* o = out + (r * n_pairs + pair) * (int64_t)S;
+    fe_pairs_item<POLAR>(ai, aj, o, pw, N, n_pad, pad_left, tw, phi0, dec, start, S, pad_mode);
 }
 
 // ------------------------------------------- pairs, pruned 8192-point FFT
@@ -324,31 +383,27 @@ __device__ __forceinline__ int xcd_item(int L, int total) {
 // P: diagnostic build stamping wave 0's wall clock at each phase boundary into
 // stamps[(b * n_pairs + pair) * 8 + phase] (vt_fe_set_pairs_stamps).
 // tab: the TW8K_* tables (cfft.h).  One (sample, pair) per workgroup, 1-D grid.
-#define PR_STAMP(i)                                                                           \
-    do {                                                                                      \
-        if constexpr (P) {                                                                    \
-            if (t == 0) stamps[((int64_t)b * n_pairs + pair) * 8 + (i)] = wall_clock64();    \
-        }                                                                                     \
+#define PR_STAMP(i)                                                              \
+    do {                                                                         \
+        if constexpr (P) {                                                       \
+            if (t == 0) stamps[((int64_t)b * n_pairs + pair) * 8 + (i)] = wall_clock64(); \
+        }                                                                        \
     } while (0)
 static constexpr int PR_ZP = PR_NB + PR_NB / 8;  // padded 512-point buffer (z512_pos)
-template <bool G, bool D = false, bool P = false, bool POLAR = true>
-__global__ __launch_bounds__(PR_T) void k_fe_pairs8k(
-    const float2* __restrict__ analytic, int n_slots, int N_, int pad_left_, int n_pairs, int B,
-    const int* __restrict__ slot_i, const int* __restrict__ slot_j, const float* __restrict__ power,
-    const float2* __restrict__ tab, const float* __restrict__ phi0, int start, int S, int pad_mode_,
-    float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+// One (row b, pair) item: ai / aj its two analytic signals, out the (rows, n_pairs, S) output (the
+// item's row of it and of the diagnostic stamps is addressed here, where the kernel always did).
+template <bool G, bool D, bool P, bool POLAR>
+__device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* aj, float* __restrict__ out,
+                                                const float pw, int N_, int pad_left_,
+                                                const float2* __restrict__ tab, const float* __restrict__ phi0,
+                                                int start, int S, int pad_mode_, const int64_t b, int n_pairs,
+                                                const int pair, unsigned long long* __restrict__ stamps) {
     static_assert(PR_T == 512, "one padded column per thread");
     const int N = G ? 4096 : N_, pad_left = G ? 2048 : pad_left_, pad_mode = G ? 0 : pad_mode_;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     float2* img = sm;               // PR_IMG
     float2* Z = sm + PR_IMG;        // PR_ZP
     const int t = threadIdx.x;
-    const int item = xcd_item(blockIdx.x, n_pairs * B);
-    const int pair = item % n_pairs;
-    const int64_t b = item / n_pairs;
-    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
-    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
-    const float pw = power[pair];
     // pass-3 output bin of this thread and its low-pass weight (loaded up front)
     const int j3 = t & 255, ka = t >> 8, k2_3 = j3 >> 4, kb_3 = j3 & 15;
     const int k3 = k2_3 + 16 * kb_3 + 256 * ka;
@@ -471,6 +526,41 @@ __global__ __launch_bounds__(PR_T) void k_fe_pairs8k(
     }
 }
 #undef PR_STAMP
+
+template <bool G, bool D = false, bool P = false, bool POLAR = true>
+__global__ __launch_bounds__(PR_T) void k_fe_pairs8k(
+    const float2* __restrict__ analytic, int n_slots, int N_, int pad_left_, int n_pairs, int B,
+    const int* __restrict__ slot_i, const int* __restrict__ slot_j, const float* __restrict__ power,
+    const float2* __restrict__ tab, const float* __restrict__ phi0, int start, int S, int pad_mode_,
+    float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+    const int N = G ? 4096 : N_;
+    const int item = xcd_item(blockIdx.x, n_pairs * B);
+    const int pair = item % n_pairs;
+    const int64_t b = item / n_pairs;
+    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    fe_pairs8k_item<G, D, P, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, b, n_pairs, pair,
+                                    stamps);
+}
+
+// Split sources (see k_fe_pairs_split): rows = B * K, row r = item / n_pairs.
+template <bool G, bool POLAR>
+__global__ __launch_bounds__(PR_T) void k_fe_pairs8k_split(
+    const float2* __restrict__ analytic_i, int n_slots_i, const float2* __restrict__ analytic_j, int n_slots_j, int K,
+    int N_, int pad_left_, int n_pairs, int rows, const int* __restrict__ slot_i, const int* __restrict__ slot_j,
+    const float* __restrict__ power, const float2* __restrict__ tab, const float* __restrict__ phi0, int start,
+    int S, int pad_mode_, float* __restrict__ out) {
+    const int N = G ? 4096 : N_;
+    const int item = xcd_item(blockIdx.x, n_pairs * rows);
+    const int pair = item % n_pairs;
+    const int64_t r = item / n_pairs;
+    const float2* ai = analytic_i + ((r / K) * n_slots_i + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic_j + (r * n_slots_j + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    fe_pairs8k_item<G, false, false, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, r,
+                                            n_pairs, pair, nullptr);
+}
 
 // Persistent form of k_fe_pairs8k<true> (the training geometry): a grid of 2 workgroups per CU,
 // each walking the items L = blockIdx.x, + gridDim.x, ... (gridDim a multiple of 8, so every
@@ -751,23 +841,15 @@ __device__ __forceinline__ void prh_parity(float2* img, float2* Z, const c2 (&y)
     }
 }
 
-// OCC: waves per SIMD the registers are fitted to (6: three workgroups per CU, 80 VGPRs; 8: four, 64)
-template <bool POLAR, int OCC, int P3 = 1>
-__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_fe_pairs8k_h(
-    const float2* __restrict__ analytic, int n_slots, int n_pairs, int B, const int* __restrict__ slot_i,
-    const int* __restrict__ slot_j, const float* __restrict__ power, const float2* __restrict__ tab,
-    const float* __restrict__ phi0, int start, int S, float* __restrict__ out) {
-    constexpr int N = 4096;
+// One (row, pair) item of the half-image form: ai / aj its two analytic signals, o its output row.
+template <bool POLAR, int OCC, int P3>
+__device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2* aj, float* __restrict__ o,
+                                                  const float pw, const float2* __restrict__ tab,
+                                                  const float* __restrict__ phi0, int start, int S) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     float2* img = sm;              // the staged product (4096), then one parity's blocks (PRH_IMG)
     float2* Z = sm + PRH_BUF;      // PR_ZP
     const int t = threadIdx.x;
-    const int item = xcd_item(blockIdx.x, n_pairs * B);
-    const int pair = item % n_pairs;
-    const int64_t b = item / n_pairs;
-    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
-    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
-    const float pw = power[pair];
     // 0: accelerated product c[u], u < N (kymatio_phase_scattering.py:211-218, :282-283)
     constexpr int LB = OCC == 6 ? 8 : 4;   // loads in flight per batch
 #pragma unroll
@@ -815,7 +897,6 @@ __global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))
     if (t < 64) {
         c2 r[8];
         wave_fft512(Z, w5, wb5, r);
-        float* o = out + (b * n_pairs + pair) * (int64_t)S;
         const float inv = 1.0f / (float)PR_NB;
         const int k0 = (t >> 3) + 8 * (t & 7);
 #pragma unroll
@@ -824,6 +905,39 @@ __global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))
             if (m >= 0 && m < S) o[m] = r[j].x * inv;
         }
     }
+}
+
+// OCC: waves per SIMD the registers are fitted to (6: three workgroups per CU, 80 VGPRs; 8: four, 64)
+template <bool POLAR, int OCC, int P3 = 1>
+__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_fe_pairs8k_h(
+    const float2* __restrict__ analytic, int n_slots, int n_pairs, int B, const int* __restrict__ slot_i,
+    const int* __restrict__ slot_j, const float* __restrict__ power, const float2* __restrict__ tab,
+    const float* __restrict__ phi0, int start, int S, float* __restrict__ out) {
+    constexpr int N = 4096;
+    const int item = xcd_item(blockIdx.x, n_pairs * B);
+    const int pair = item % n_pairs;
+    const int64_t b = item / n_pairs;
+    const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    fe_pairs8k_h_item<POLAR, OCC, P3>(ai, aj, out + (b * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
+}
+
+// Split sources (see k_fe_pairs_split): rows = B * K, row r = item / n_pairs.
+template <bool POLAR, int OCC, int P3 = 1>
+__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_fe_pairs8k_h_split(
+    const float2* __restrict__ analytic_i, int n_slots_i, const float2* __restrict__ analytic_j, int n_slots_j, int K,
+    int n_pairs, int rows, const int* __restrict__ slot_i, const int* __restrict__ slot_j,
+    const float* __restrict__ power, const float2* __restrict__ tab, const float* __restrict__ phi0, int start,
+    int S, float* __restrict__ out) {
+    constexpr int N = 4096;
+    const int item = xcd_item(blockIdx.x, n_pairs * rows);
+    const int pair = item % n_pairs;
+    const int64_t r = item / n_pairs;
+    const float2* ai = analytic_i + ((r / K) * n_slots_i + slot_i[pair]) * (int64_t)N;
+    const float2* aj = analytic_j + (r * n_slots_j + slot_j[pair]) * (int64_t)N;
+    const float pw = power[pair];
+    fe_pairs8k_h_item<POLAR, OCC, P3>(ai, aj, out + (r * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
 }
 
 // ------------------------------------------- wavelets, 8192-point register FFT
@@ -1202,6 +1316,21 @@ int vt_fe_spectrum(const float* x, int64_t rows, int N, int n_pad, int pad_left,
     return VT_OK;
 }
 
+int vt_fe_spectrum_rolled(const float* x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left,
+                          int pad_mode, const int* shifts, int K, const void* tw, void* xhat, void* stream) {
+    VT_CHECK_ARG(pow2(n_pad) && n_pad <= VT_FFT_MAX_LDS && n_pad >= N, "vt_fe_spectrum_rolled: n_pad=%d", n_pad);
+    VT_CHECK_ARG(B > 0 && K > 0 && N > 1 && pad_mode >= 0 && pad_mode <= 2 && pad_left >= 0 && x_row_stride >= N,
+                 "vt_fe_spectrum_rolled: B/K/N/pad/stride");
+    VT_CHECK_ARG(B * K < (1ll << 31), "vt_fe_spectrum_rolled: grid");
+    VT_CHECK_ARG(x != nullptr && shifts != nullptr && tw != nullptr && xhat != nullptr,
+                 "vt_fe_spectrum_rolled: null pointer");
+    hipLaunchKernelGGL(k_fe_spectrum_rolled, dim3((unsigned)(B * K)), dim3(FE_THREADS), fft_lds_bytes(n_pad),
+                       S(stream), x, x_row_stride, N, n_pad, pad_left, pad_mode, shifts, K, (const float2*)tw,
+                       (float2*)xhat);
+    VT_LAUNCH_CHECK("vt_fe_spectrum_rolled");
+    return VT_OK;
+}
+
 int vt_fe_lowpass(const float* x, int64_t rows, int64_t x_row_stride, int N, int n_pad, int pad_left,
                   const float* h0, int radius, int step, int start, int S_out, float* out, int64_t out_row_stride,
                   void* stream) {
@@ -1403,6 +1532,64 @@ int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, 
                            (const float2*)tw, phi0, dec, start, S_out, pad_mode, out);
     }
     VT_LAUNCH_CHECK("vt_fe_pairs");
+    return VT_OK;
+}
+
+// vt_fe_pairs with split sources.  The kernel family follows vt_fe_pairs's choice for the same
+// geometry and settings, so a row's bits are those of vt_fe_pairs on the same two signals: the
+// half-image form on the training geometry (vt_fe_set_pairs_half), the full-image form when that is
+// off or the persistent form (the same bits) would be chosen, and for other 8192-padded geometries,
+// the generic kernel elsewhere.  The direct-column and stamping diagnostics have no split form.
+int vt_fe_pairs_split(const void* analytic_i, int n_slots_i, const void* analytic_j, int n_slots_j, int64_t B, int K,
+                      int N, int n_pad, int pad_left, int n_pairs, const int* slot_i, const int* slot_j,
+                      const float* power, const void* tw, const float* phi0, int dec, int start, int S_out,
+                      int pad_mode, float* out, void* stream) {
+    VT_CHECK_ARG(pow2(n_pad) && n_pad <= VT_FFT_MAX_LDS, "vt_fe_pairs_split: n_pad=%d", n_pad);
+    VT_CHECK_ARG(dec == 0 ? S_out == N : (dec >= 1 && pow2(dec) && n_pad / dec >= start + S_out),
+                 "vt_fe_pairs_split: dec/start (decimation must be a power of two)");
+    VT_CHECK_ARG(B > 0 && K > 0 && n_pairs > 0 && n_slots_i > 0 && n_slots_j > 0 && N > 0 && pad_mode >= 0 &&
+                     pad_mode <= 2,
+                 "vt_fe_pairs_split: empty/pad_mode");
+    VT_CHECK_ARG(analytic_i != nullptr && analytic_j != nullptr && slot_i != nullptr && slot_j != nullptr &&
+                     power != nullptr && phi0 != nullptr && out != nullptr,
+                 "vt_fe_pairs_split: null pointer");
+    const int64_t rows = B * K;
+    VT_CHECK_ARG(rows * n_pairs < (1ll << 31), "vt_fe_pairs_split: grid");
+    const float2 *Ai = (const float2*)analytic_i, *Aj = (const float2*)analytic_j;
+    if (dec == PR_N / PR_NB && n_pad == PR_N && start + S_out <= PR_NB && N <= PR_IMG) {
+        const bool geo = N == 4096 && pad_left == 2048 && pad_mode == 0;
+        const bool pol = analytic_polar(n_pad, N, pad_left);
+        const float2* tab = tw8k_tables(S(stream));
+        VT_CHECK_ARG(tab != nullptr, "vt_fe_pairs_split: twiddle tables unavailable (first call under stream capture?)");
+        const int64_t total = rows * n_pairs;
+        const int pgrid = pairs_persist_grid();
+        const bool persist = pgrid > 0 && total >= 2 * pgrid;   // vt_fe_pairs would run k_fe_pairs8k<true>'s bits
+        const int hf = pairs_half();
+        if (geo && !persist && hf) {
+            hipLaunchKernelGGL(pol ? (hf == 2   ? k_fe_pairs8k_h_split<true, 8>
+                                      : hf == 3 ? k_fe_pairs8k_h_split<true, 6, 0>
+                                                : k_fe_pairs8k_h_split<true, 6>)
+                                   : (hf == 2   ? k_fe_pairs8k_h_split<false, 8>
+                                      : hf == 3 ? k_fe_pairs8k_h_split<false, 6, 0>
+                                                : k_fe_pairs8k_h_split<false, 6>),
+                               dim3((unsigned)total), dim3(PR_T), PRH_LDS, S(stream), Ai, n_slots_i, Aj, n_slots_j, K,
+                               n_pairs, (int)rows, slot_i, slot_j, power, tab, phi0, start, S_out, out);
+        } else {
+            hipLaunchKernelGGL(pol ? (geo ? k_fe_pairs8k_split<true, true> : k_fe_pairs8k_split<false, true>)
+                                   : (geo ? k_fe_pairs8k_split<true, false> : k_fe_pairs8k_split<false, false>),
+                               dim3((unsigned)total), dim3(PR_T), (PR_IMG + PR_ZP) * sizeof(float2), S(stream), Ai,
+                               n_slots_i, Aj, n_slots_j, K, N, pad_left, n_pairs, (int)rows, slot_i, slot_j, power,
+                               tab, phi0, start, S_out, pad_mode, out);
+        }
+    } else {
+        VT_CHECK_ARG(tw != nullptr, "vt_fe_pairs_split: null twiddles");
+        VT_CHECK_ARG(rows <= 65535, "vt_fe_pairs_split: rows=%lld > 65535 (grid y)", (long long)rows);
+        hipLaunchKernelGGL(analytic_polar(n_pad, N, pad_left) ? k_fe_pairs_split<true> : k_fe_pairs_split<false>,
+                           dim3(n_pairs, (unsigned)rows), dim3(FE_THREADS), fft_lds_bytes(n_pad), S(stream), Ai,
+                           n_slots_i, Aj, n_slots_j, K, N, n_pad, pad_left, n_pairs, slot_i, slot_j, power,
+                           (const float2*)tw, phi0, dec, start, S_out, pad_mode, out);
+    }
+    VT_LAUNCH_CHECK("vt_fe_pairs_split");
     return VT_OK;
 }
 

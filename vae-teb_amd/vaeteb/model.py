@@ -814,6 +814,17 @@ class SeqVaeTeb(nn.Module):
             torch.randn_like(lv_q)
             return self._kld_loss(mu_p, lv_p, mu_q, lv_q, reduce_mean=reduce_mean)
 
+    def transfer_entropy_vs_shift(self, frontend, x, shifts=None, **kw):
+        """Transfer entropy of every recording of x (B, 2, N) against circular shifts of its up
+        channel (ref/model/graph_model.py:1210-1458), batched over (recording, shift):
+        vaeteb.te.ShiftSweep(self, frontend)(x, shifts, **kw), the sweep kept for the next call
+        with the same front-end.  shifts: samples (default vaeteb.te.left_shifts(): 0 .. -60 s)."""
+        from .te import ShiftSweep, left_shifts
+        sweep = self.__dict__.get("_shift_sweep")
+        if sweep is None or sweep.frontend is not frontend:
+            sweep = self.__dict__["_shift_sweep"] = ShiftSweep(self, frontend)
+        return sweep(x, left_shifts() if shifts is None else shifts, **kw)
+
     @staticmethod
     def get_predictions(x, stride=16, new_C=4800):
         """ref/model/vae_teb_model.py:1228-1246: overlapping per-step windows x (B, N, C)
