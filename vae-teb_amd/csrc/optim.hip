@@ -353,11 +353,16 @@ __global__ void k_adamw_coef(int* step, float lr, float beta1, float beta2, floa
     coef[1] = (float)sqrt(bc2);
 }
 
-// bf16 shadow of the parameters for the MFMA GEMM operands (round-to-nearest-even).
+// bf16 shadow of the parameters for the MFMA GEMM operands (round-to-nearest-even).  A NaN stays
+// a (quiet) NaN of its sign: the rounding add would carry a large payload into the exponent and
+// the sign (0x7FFFFFFF -> -0) or drop a small one (0x7F800001 -> +inf), and the bf16 gradient
+// all-reduce would then hide an overflow from the inf check behind it.
 __global__ void k_cast_bf16(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t u = __float_as_uint(src[i]);
-        dst[i] = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+        const bool nan = (u & 0x7FFFFFFFu) > 0x7F800000u;
+        dst[i] = nan ? (uint16_t)(((u >> 16) & 0x8000u) | 0x7FC0u)
+                     : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     }
 }
 
