@@ -308,6 +308,30 @@ int vt_scale_by_device_scalar(float* x, int64_t n, const float* s, void* stream)
  *           kld_tensor.mean() ref/model/graph_model.py:1371, once per shift                       */
 int vt_te_kl_rows(const float* mu_c, const float* lv_q, const float* mu_y, const float* lv_p, int64_t B, int K,
                   int64_t row_elems, float* te, float* kl, void* stream);
+/* Evaluation sweep (vaeteb/evaluate.py), B*K (recording, gain) rows r = b*K + k.  As vt_te_kl_rows: one
+ * workgroup per row, fixed-order sums in double, no atomics, identical run to run and under any
+ * split of the rows over calls.
+ * x (B, row_elems), gains: K device floats; out[(b*K + k), i] = x[b, i] * gains[k], the IEEE product
+ * (float4 accesses on rows whose source and destination are 16-byte aligned, scalar tail).
+ * replaces: x_scaled = x_ph_base * float(g) ref/model/graph_model.py:1833, once per gain       */
+int vt_eval_scale_rows(const float* x, int64_t B, int K, int64_t row_elems, const float* gains, float* out,
+                       void* stream);
+/* vt_te_kl_rows with the reparameterisation: mu_c, lv_q, eps (B*K, S, L); prior mu_y, lv_p (B, S, L) read
+ * at row r / K.  mu_post (nullable) = mu_c + mu_y; z = mu_post + eps*exp(0.5*lv_q) (vt_elbo_latent_fwd's
+ * expression and order: the same bits for the same inputs); te[r] and kl (nullable) are vt_te_kl_rows's.
+ * replaces: SeqVaeTeb.reparameterize ref/model/vae_teb_model.py:1046-1050, the residual :1115, and
+ *           measure_transfer_entropy(reduce_mean=False) :1194-1226 + its per-sample mean
+ *           ref/model/graph_model.py:1602, :1836-1839, once per gain                              */
+int vt_te_latent_rows(const float* mu_c, const float* lv_q, const float* mu_y, const float* lv_p, const float* eps,
+                      int64_t B, int K, int64_t row_elems, float* z, float* mu_post, float* te, float* kl,
+                      void* stream);
+/* Reconstruction metrics: y (B, n) the ground truth read at row r / K, pr (B*K, n); out (B*K, 4) =
+ * {vaf, mse, snr_db, vaf_unclamped}.  res = y - pr in fp32 (numpy's float32 subtraction), the rest in
+ * double: var_y, var_res population variances (two passes, centred), mse = mean(res^2), sig = mean(y^2);
+ * vaf_unclamped = var_y > 1e-12 ? 1 - var_res/var_y : 0; vaf = clamp(vaf_unclamped, 0, 1);
+ * snr_db = mse > 1e-12 ? 10*log10(sig/mse) : 100.
+ * replaces: the per-sample numpy metrics ref/model/graph_model.py:1606-1645 and :1842-1851      */
+int vt_recon_metrics_rows(const float* y, const float* pr, int64_t B, int K, int64_t n, float* out, void* stream);
 
 /* ----------------------------------------------------------------- optimiser
  * Flat fp32 buffers: every parameter / gradient / moment is a view of one

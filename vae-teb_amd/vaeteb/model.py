@@ -825,6 +825,40 @@ class SeqVaeTeb(nn.Module):
             sweep = self.__dict__["_shift_sweep"] = ShiftSweep(self, frontend)
         return sweep(x, left_shifts() if shifts is None else shifts, **kw)
 
+    def up_gain_sweep(self, y_st=None, y_ph=None, x_ph=None, y_raw=None, gains=None, frontend=None, x=None, **kw):
+        """Transfer entropy and reconstruction metrics (VAF / MSE / SNR of mu_pr against y_raw) of
+        every recording under multiplicative gains on its normalised UP features
+        (ref/model/graph_model.py:1779-1870), batched over (recording, gain):
+        vaeteb.evaluate.GainSweep(self)(y_st, y_ph, x_ph, y_raw, gains, **kw), the sweep kept for the
+        next call.  gains: default vaeteb.evaluate.DEFAULT_GAINS, the reference's [0, .5, 1, 1.5, 2].
+        With frontend=fe, x=windows (B, 2, N) in place of the four fields they are taken from fe(x),
+        as Trainer.step({"x": ...}) takes them.  Returns an EvalSweepResult."""
+        from .evaluate import DEFAULT_GAINS, GainSweep
+        if (frontend is None) != (x is None):
+            raise ValueError("frontend= and x= go together")
+        if frontend is not None:
+            if any(t is not None for t in (y_st, y_ph, x_ph, y_raw)):
+                raise ValueError("give either the four fields or frontend= and x=, not both")
+            f = frontend(x)
+            y_st, y_ph, x_ph, y_raw = f["fhr_st"], f["fhr_ph"], f["fhr_up_ph"], f["fhr"]
+        elif any(t is None for t in (y_st, y_ph, x_ph, y_raw)):
+            raise ValueError("y_st, y_ph, x_ph and y_raw are all required (or frontend= and x=)")
+        sweep = self.__dict__.get("_gain_sweep")
+        if sweep is None:
+            sweep = self.__dict__["_gain_sweep"] = GainSweep(self)
+        return sweep(y_st, y_ph, x_ph, y_raw, DEFAULT_GAINS if gains is None else gains, **kw)
+
+    def up_ablation(self, y_st=None, y_ph=None, x_ph=None, y_raw=None, **kw):
+        """The UP ablation (ref/model/graph_model.py:1682-1777): up_gain_sweep with gains (1, 0),
+        column 0 the intact features, column 1 the UP features zeroed."""
+        from .evaluate import ABLATION_GAINS
+        return self.up_gain_sweep(y_st, y_ph, x_ph, y_raw, gains=ABLATION_GAINS, **kw)
+
+    def reconstruction_metrics(self, y_st=None, y_ph=None, x_ph=None, y_raw=None, **kw):
+        """The per-recording values of the metrics histogram analysis (ref/model/graph_model.py:
+        1510-1680): up_gain_sweep with the single gain 1, every result (B, 1)."""
+        return self.up_gain_sweep(y_st, y_ph, x_ph, y_raw, gains=(1.0,), **kw)
+
     @staticmethod
     def get_predictions(x, stride=16, new_C=4800):
         """ref/model/vae_teb_model.py:1228-1246: overlapping per-step windows x (B, N, C)
