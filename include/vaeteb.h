@@ -210,6 +210,28 @@ int vt_stats_accum(const float* in, int64_t B, int C, int in_C, int in_S, int s0
 int vt_stats_accum_raw(const float* x, int64_t rows, int64_t row_stride, int N, int64_t* count, double* sum,
                        double* sum_sq, void* work, int64_t work_bytes, void* stream);
 
+/* --------------------------------------------------- recordings -> windows
+ * A row is one channel of one window: N consecutive floats at base + row_off[r] (row_off:
+ * device int64[rows], element offsets; rows may overlap and start at any element, no
+ * alignment assumed).  Neither call reads outside [row_off[r], row_off[r] + N).  Both are
+ * no-ops for rows == 0 and return VT_ERR_ARG, before any device work, for N < 1,
+ * min_length < 1, rows < 0 or a null pointer with rows > 0.
+ *
+ * vt_window_flat_stats: out[r] = {longest, total length, number} of the qualifying flat
+ * regions of row r.  Diff i (1 <= i < N) is flat iff (double)fabsf(x[i] - x[i-1]) <= tolerance
+ * (NaN and inf - inf are not flat); a maximal run of m >= 1 flat diffs is a region of m + 1
+ * samples and qualifies iff m + 1 >= min_length; a run open at the last sample ends there.
+ * Exact (integers).  One wave per row, no LDS, no atomics.
+ * replaces: find_flat_regions + the length arithmetic
+ *           (ref/hdf5_dataset/create_hdf5_dataset.py:46-81, :462-472)                      */
+int vt_window_flat_stats(const float* base, const int64_t* row_off, int64_t rows, int N, double tolerance,
+                         int min_length, int32_t* out, void* stream);
+/* out[r][0..N) = row r, bit for bit (out: rows x N contiguous).  With rows ordered (window,
+ * channel) out is the (B, 2, N) batch of vt_fe_spectrum.
+ * replaces: np.stack([fhr, up], axis=1) of the prepared blocks
+ *           (ref/hdf5_dataset/create_hdf5_dataset.py:405-418)                              */
+int vt_window_gather(const float* base, const int64_t* row_off, int64_t rows, int N, float* out, void* stream);
+
 /* kymatio backend-plugin primitives (TorchBackend1D, ref/kymatio/kymatio/scattering1d/
  * backend/torch_backend.py:17-174 and ref/kymatio/kymatio/backend/torch_backend.py:99-219) */
 int vt_fft(const void* in, void* out, int64_t rows, int n, int inverse, const void* tw, int tw_stride,
