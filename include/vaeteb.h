@@ -136,10 +136,9 @@ int vt_fe_pairs_split(const void* analytic_i, int n_slots_i, const void* analyti
  * default: measured faster in the step); returns the previous grid (same bits either way) */
 int vt_fe_set_pairs_persist(int grid);
 int vt_fe_set_pairs_direct(int on);
-/* pair kernel form on the training geometry: 1 = half-image k_fe_pairs8k_h at three workgroups per CU
- * (default), 2 = the same at four (64 VGPRs), 3 = three per CU with the four-lane pass 3, 0 = the
- * full-image k_fe_pairs8k of rounds 2-5; initial value from VAETEB_PAIRS_HALF; returns the previous
- * setting */
+/* pair kernel form on the training geometry: 1 (any positive value) = half-image k_fe_pairs8k_h at
+ * three workgroups per CU (default), 0 = the full-image k_fe_pairs8k of rounds 2-5; initial value
+ * from VAETEB_PAIRS_HALF; returns the previous setting (0 or 1) */
 int vt_fe_set_pairs_half(int on);
 /* Storage form of the analytic slots on the 8192-point geometry (n_pad 8192,
  * pad_left + N <= 8192), shared by vt_fe_wavelet (writes) and vt_fe_pairs (reads):
@@ -148,11 +147,6 @@ int vt_fe_set_pairs_half(int on);
  * 0 = complex {re, im} (every other geometry is always complex).  Default 1;
  * VAETEB_ANALYTIC_POLAR=0 sets 0 initially; returns the previous setting.  Not thread-safe.  */
 int vt_fe_set_analytic_polar(int on);
-
-/* Diagnostic (tools/pairs_phases.py): while buf != NULL, training-geometry vt_fe_pairs
- * launches stamp wave 0's wall clock (100 MHz) at each phase boundary into
- * buf[(b * n_pairs + pair) * 8 + phase] (uint64).  NULL turns it off. */
-int vt_fe_set_pairs_stamps(void* buf);
 
 /* Per-channel transform (kind 0 none, 1 log(max(x,0)+log_eps), 2 asinh) and
  * z-score (x-mean)/(std+1e-8); in[b, c, s] (batch stride in_C*S) -> out[b, s, out_off + c]
@@ -797,7 +791,7 @@ int vt_lstm16_layer_bwd(const float* dh_out, const float* gates, const float* cs
  * layer l + 1 runs one 16-step chunk behind layer l in the same workgroup (8 waves, the
  * chunk's h handed over in LDS), S + 16 steps instead of 2 S.  Outputs are exactly two
  * vt_lstm16_layer_fwd calls' (out_hprev omitted), bit for bit.  In % 4 == 0, In <= 64;
- * layer l's input is staged in LDS: seq <= 416 (VAETEB_L16_PAIR_NS=4: <= 208).
+ * layer l's input is staged in LDS: seq <= 416.
  * replaces: two layers of nn.LSTM(num_layers=4) under torch.amp.autocast
  *           (vae_teb_model.py:474-480, :647-653)                                   */
 int vt_lstm16_pair_fwd(const float* x, int In, const float* w_ih0, const float* b_ih0, const float* w_hh0,
@@ -823,7 +817,7 @@ int vt_lstm16_pair_bwd(const float* dh_out, const float* gates1, const float* c1
  * chunks of steps instead of 2 (S + 1 chunk).  params: the 16 pointers [w_ih, w_hh, b_ih,
  * b_hh] of layers 0..3; outs: the 12 pointers [h, c, gates] of layers 0..3.  Outputs are
  * exactly two vt_lstm16_pair_fwd calls', bit for bit (which it runs instead when the
- * workgroups per pair are not a multiple of 8, or VAETEB_L16_CHAIN=0).
+ * workgroups per pair are not a multiple of 8).
  * replaces: nn.LSTM(in, 64, 4 layers) under torch.amp.autocast (vae_teb_model.py:474-480,
  *           :647-653)                                                                   */
 int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B, int seq, int hidden,

@@ -31,3 +31,32 @@ def test_argument_errors_map_to_value_error():
 
 def test_library_is_in_tree():
     assert os.path.commonpath([_lib.LIB_PATH, os.path.dirname(os.path.dirname(__file__))])
+
+
+def test_documented_switches_are_read_by_the_package():
+    """Every VAETEB_* name that INTEGRATION.md, include/vaeteb.h or a file under tools/ mentions is
+    read somewhere in the package's sources (a .hip / .cpp / .h / .py file under vae-teb_amd/), so
+    that documents and tools cannot go on naming a switch that no longer exists.  The header's own
+    include guard is no switch."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name = re.compile(r"VAETEB_[A-Z0-9_]+")
+    header = open(os.path.join(root, "include", "vaeteb.h")).read()
+    guards = set(re.findall(r"^#\s*(?:ifndef|define)\s+(VAETEB_[A-Z0-9_]+)\s*$", header, re.M))
+    docs = [os.path.join(root, "INTEGRATION.md"), os.path.join(root, "include", "vaeteb.h")]
+    for d, _, files in os.walk(os.path.join(root, "tools")):
+        docs += [os.path.join(d, f) for f in files]
+    named = {}
+    for path in docs:
+        with open(path, errors="replace") as fh:
+            for n in name.findall(fh.read()):
+                named.setdefault(n, os.path.relpath(path, root))
+    read = set()
+    for d, _, files in os.walk(os.path.join(root, "vae-teb_amd")):
+        for f in files:
+            if f.endswith((".hip", ".cpp", ".h", ".py")):
+                with open(os.path.join(d, f), errors="replace") as fh:
+                    read.update(name.findall(fh.read()))
+    stale = {n: where for n, where in named.items() if n not in read and n not in guards}
+    assert len(named) >= 20 and read, (len(named), len(read))
+    assert not stale, stale

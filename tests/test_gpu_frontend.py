@@ -304,6 +304,26 @@ def test_pairs_persistent_kernel_bitwise(fe11, B):
     assert torch.equal(got, ref) and torch.equal(got_small, ref)
 
 
+def test_pairs_half_setter_normalises_to_one_form(fe11):
+    """vt_fe_set_pairs_half keeps one half-image form: any positive argument (3 once selected a
+    measured-and-rejected variant) reads back as 1 and runs form 1's kernel, bit for bit.  B = 1 on
+    the J = 11 Q = 4 T = 16 N = 4096 plan: the smallest input that takes the half-image path."""
+    from vaeteb import _lib, synthetic
+    fns = _lib.lib().fns
+    x = torch.from_numpy(synthetic.batch(5151, 1, 4096)).cuda()
+    prev = fns["vt_fe_set_pairs_half"](1)
+    try:
+        one = fe11.raw(x)["pairs"].clone()
+        assert fns["vt_fe_set_pairs_half"](3) == 1
+        assert fns["vt_fe_set_pairs_half"](3) == 1     # the 3 just set reads back as 1
+        three = fe11.raw(x)["pairs"].clone()
+    finally:
+        fns["vt_fe_set_pairs_half"](prev)
+    torch.cuda.synchronize()
+    assert torch.isfinite(one).all() and one.abs().max().item() > 0
+    assert torch.equal(three, one)
+
+
 @pytest.mark.parametrize("B", [4, 8])
 def test_pairs_full_image_kernel_vs_oracle(fe11, B):
     """The full-image pair kernel (k_fe_pairs8k, vt_fe_set_pairs_half(0), the default of rounds

@@ -1,7 +1,7 @@
 """BatchNorm backward kernels of the conv blocks at the decoder / encoder shapes (B = 256):
 vt_batchnorm_bwd_coef (k_col_partial4 + k_bn_finalize) and vt_batchnorm_bwd_x16
 (k_bn_bwd_x16), HIP-event time per launch and HBM GB/s of the compulsory bytes, plus a
-checksum of the bf16 rows (compare runs under VAETEB_BNX16_PF=0 / 1: same bits).
+checksum of the bf16 rows (to compare two builds: same bits).
 usage: bn_micro.py"""
 import os
 import sys

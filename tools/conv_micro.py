@@ -10,7 +10,7 @@ import torch  # noqa: E402
 from vaeteb import _lib  # noqa: E402
 from vaeteb.model import ConvBlock, Decoder  # noqa: E402
 
-_lib.call("vt_conv_bf16_set_staging", int(os.environ.get("VAETEB_CONV_CL", "1")))   # window staging A/B
+_lib.call("vt_conv_bf16_set_staging", int(os.environ.get("CONV_MICRO_STAGING", "1")))   # window staging A/B
 
 B, L = 256, 256
 dev = "cuda"

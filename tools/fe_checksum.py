@@ -1,5 +1,5 @@
 """SHA-256 of the training-geometry front-end's features (J=11 Q=4 T=16, N=4096, B=64, seeded
-synthetic windows): run under two kernel-selection settings (e.g. VAETEB_WAVELET_LP=0 / 1) to
+synthetic windows): run under two kernel-selection settings (e.g. VAETEB_PAIRS_PERSIST=0 / -1) to
 check that a variant writes the same bits."""
 import hashlib
 import os

@@ -12,6 +12,6 @@ run() {
   [ $rc -eq 0 ] || [ $rc -eq 1 ]
 }
 rm -f gpurun_out/ddpab/summary.txt
-run VAETEB_X=1 fix1 && run VAETEB_X=1 fix2 && run VAETEB_X=1 fix3 && run VAETEB_DDP_DIAG=1 join1 && \
+run NO_SETTING=1 fix1 && run NO_SETTING=1 fix2 && run NO_SETTING=1 fix3 && run VAETEB_DDP_DIAG=1 join1 && \
 timeout -k 10 400 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests/test_gpu_ddp.py > gpurun_out/ddpab/file.log 2>&1
 cat gpurun_out/ddpab/summary.txt

@@ -1,4 +1,4 @@
-"""J=6 front-end outputs per pair-kernel form (vt_fe_set_pairs_half 0 / 1 / 3), with and without the
+"""J=6 front-end outputs per pair-kernel form (vt_fe_set_pairs_half 0 / 1), with and without the
 side stream the trainer uses: max |difference| per output field against form 0 without a side
 stream.  Usage: python tools/j6_pairs_diag.py"""
 import os
@@ -16,7 +16,7 @@ for J, Q in ((6, 1), (11, 4)):
     x = torch.from_numpy(synthetic.batch(4244, 2, 4096)).cuda()
     side = torch.cuda.Stream()
     res = {}
-    for form in (0, 1, 3):
+    for form in (0, 1):
         fns["vt_fe_set_pairs_half"](form)
         for sd in (None, side):
             o = {k: v.clone() for k, v in fe(x, side=sd).items()}

@@ -25,8 +25,6 @@
 //         mirrors, then the adjoint of the linear upsample with its four fixed weights, in
 //         k_conv_fold's order: the same bits) is applied there; each workgroup owns TS input
 //         rows and computes the 2 TS + pad + 2 padded rows they read.
-#include <stdlib.h>
-
 #include "conv.h"
 #include "h16.h"
 
@@ -387,17 +385,16 @@ int vt_batchnorm_bwd_x16(const float* dY, const float* Xc, const float* bnp, int
     const int c32 = cdiv(C, 32) * 32;
     // rows per block: 256 for the narrowest layers (C <= 4: one 64-row block is only 1 KB per
     // stream; measured C = 1, M = 1 M: 19.9 -> 15.1 us), 64 otherwise (C = 32: 5.4 vs 9.4 us);
-    // VAETEB_BNX16_ROWS = 64 / 256 forces one (tools/bn_micro.py; the same bits either way)
-    static const int xrb_env = getenv("VAETEB_BNX16_ROWS") ? atoi(getenv("VAETEB_BNX16_ROWS")) : 0;
-    const int xrb = xrb_env == 256 || xrb_env == 64 ? xrb_env : (C <= 4 ? 256 : 64);
+    // the same bits either way
+    const int xrb = C <= 4 ? 256 : 64;
     const size_t lds = (size_t)8 * ((C + 3) & ~3) * 4 + (size_t)xrb * c32 * 2;
     VT_CHECK_ARG(lds <= 160 * 1024, "vt_batchnorm_bwd_x16: C too large");
     // at most 8 workgroups per CU of 64-row blocks, each walking several blocks: the per-workgroup
     // parameter staging (6 C loads + a barrier) is paid once per workgroup, not per block
     // (the same element computation: the same bits)
     const int64_t blocks = (M + xrb - 1) / xrb;
-    static const int cap = getenv("VAETEB_BNX16_GRID") ? atoi(getenv("VAETEB_BNX16_GRID")) : 2048;
-    const dim3 grid((unsigned)(blocks < cap ? blocks : cap));
+    constexpr int BNX16_GRID = 2048;
+    const dim3 grid((unsigned)(blocks < BNX16_GRID ? blocks : BNX16_GRID));
     const float invM = 1.f / (float)M;
     hipStream_t st = S(stream);
 #define VT_BNX(A, R) hipLaunchKernelGGL((k_bn_bwd_x16<H, A, R>), grid, dim3(256), lds, st, dY, Xc, bnp, M, C, c32, invM, (H*)d16)

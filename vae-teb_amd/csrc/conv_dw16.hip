@@ -3,8 +3,6 @@
 // one translation unit per kernel family, so the builds run in parallel).  The staging
 // conventions (window padding / x2 upsample via conv.h, the previous block's BatchNorm via
 // bnbwd.h for the conv-stack fold) are shared with the forward kernels.
-#include <stdlib.h>
-
 #include "conv.h"
 #include "h16.h"
 
@@ -399,10 +397,10 @@ static int bwd_weight(const float* dY, const float* X, int B, int L_in, int Cin,
     const int bx = cdiv(npairs, nwv * ppw);
     const int64_t rows = (int64_t)B * g.L_out;
     const int64_t nout = (int64_t)Cout * Cin * K;
-    // workgroup budget of the row splits (VAETEB_CONVDW_WG, default 8192; measured 4096 -> 8192:
-    // 8.80-8.85 -> 8.78-8.79 ms, 1024: 9.2 ms — the weight gradients join the step's end)
-    static const int wg_budget = getenv("VAETEB_CONVDW_WG") ? atoi(getenv("VAETEB_CONVDW_WG")) : 8192;
-    int64_t splits = (wg_budget > 0 ? wg_budget : 4096) / (nwv * bx);
+    // workgroup budget of the row splits (measured 4096 -> 8192: 8.80-8.85 -> 8.78-8.79 ms,
+    // 1024: 9.2 ms — the weight gradients join the step's end)
+    constexpr int CONVDW_WG = 8192;
+    int64_t splits = CONVDW_WG / (nwv * bx);
     if (splits > 1024) splits = 1024;   // the two-stage split sum handles <= 32^2
     if (splits * nout > (int64_t)8 << 20) splits = ((int64_t)8 << 20) / nout;
     if (splits > rows / (4 * DWR)) splits = rows / (4 * DWR);

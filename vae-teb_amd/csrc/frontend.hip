@@ -380,24 +380,16 @@ __device__ __forceinline__ int xcd_item(int L, int total) {
 // length and pad index a compile-time constant (no bounds checks, the reflection
 // of each radix-16 column is known per n2); otherwise the runtime arguments.
 // D: product columns formed straight from HBM / L2 (no LDS staging pass).
-// P: diagnostic build stamping wave 0's wall clock at each phase boundary into
-// stamps[(b * n_pairs + pair) * 8 + phase] (vt_fe_set_pairs_stamps).
 // tab: the TW8K_* tables (cfft.h).  One (sample, pair) per workgroup, 1-D grid.
-#define PR_STAMP(i)                                                              \
-    do {                                                                         \
-        if constexpr (P) {                                                       \
-            if (t == 0) stamps[((int64_t)b * n_pairs + pair) * 8 + (i)] = wall_clock64(); \
-        }                                                                        \
-    } while (0)
 static constexpr int PR_ZP = PR_NB + PR_NB / 8;  // padded 512-point buffer (z512_pos)
 // One (row b, pair) item: ai / aj its two analytic signals, out the (rows, n_pairs, S) output (the
-// item's row of it and of the diagnostic stamps is addressed here, where the kernel always did).
-template <bool G, bool D, bool P, bool POLAR>
+// item's row of it is addressed here, where the kernel always did).
+template <bool G, bool D, bool POLAR>
 __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* aj, float* __restrict__ out,
                                                 const float pw, int N_, int pad_left_,
                                                 const float2* __restrict__ tab, const float* __restrict__ phi0,
                                                 int start, int S, int pad_mode_, const int64_t b, int n_pairs,
-                                                const int pair, unsigned long long* __restrict__ stamps) {
+                                                const int pair) {
     static_assert(PR_T == 512, "one padded column per thread");
     const int N = G ? 4096 : N_, pad_left = G ? 2048 : pad_left_, pad_mode = G ? 0 : pad_mode_;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
@@ -408,7 +400,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
     const int j3 = t & 255, ka = t >> 8, k2_3 = j3 >> 4, kb_3 = j3 & 15;
     const int k3 = k2_3 + 16 * kb_3 + 256 * ka;
     const float ph3 = phi0[k3];
-    PR_STAMP(0);
     c2 v[16], w[15];
     // the pass-1 twiddles W_8192^{t k2}: issued before the barriers of the column formation
     // (no dependence on it), so their L2 latency overlaps the waits instead of following them
@@ -449,7 +440,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
                 if (G || u < N) img[u] = pair_prod<POLAR>(xa[k], xb[k], pw);
             }
         }
-        PR_STAMP(1);
         load_w1();
         __syncthreads();
         // 1: column n1 = t of the padded signal (reflect / zero / circular); one
@@ -470,7 +460,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
 #pragma unroll
         for (int k2 = 1; k2 < 16; ++k2) img[pr_pos(t + 512 * k2)] = F2(pmul(v[k2], w[k2 - 1]));
     }
-    PR_STAMP(2);
     // the pass-2 twiddles W_512^{n1a kb}, likewise in flight across the barrier
 #pragma unroll
     for (int kb = 1; kb < 16; ++kb) w[kb - 1] = C2(tab[TW8K_T2 + 32 * (kb - 1) + (t & 31)]);
@@ -487,7 +476,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
 #pragma unroll
         for (int kb = 1; kb < 16; ++kb) base[33 * kb] = F2(pmul(x[kb], w[kb - 1]));
     }
-    PR_STAMP(3);
     __syncthreads();
     // 3: (k2, k'b) = (j >> 4, j & 15), j = t & 255: output k'a = t >> 8 (0 or 1) of the
     // radix-32 stage; Z holds conj(X phi0) so that the 512-point inverse below is a
@@ -504,7 +492,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
         }
         Z[z512_pos(k3)] = make_float2(x.x * ph3, -x.y * ph3);
     }
-    PR_STAMP(4);
     // wave 0's 512-point twiddles in flight across the barrier
     c2 w5[7], wb5[7];
     if (t < 64) fft512_twiddles(tab, w5, wb5);
@@ -513,7 +500,6 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
     if (t < 64) {
         c2 r[8];
         wave_fft512(Z, w5, wb5, r);
-        PR_STAMP(5);
         float* o = out + (b * n_pairs + pair) * (int64_t)S;
         const float inv = 1.0f / (float)PR_NB;
         const int k0 = (t >> 3) + 8 * (t & 7);
@@ -522,17 +508,16 @@ __device__ __forceinline__ void fe_pairs8k_item(const float2* ai, const float2* 
             const int m = k0 + 64 * j - start;
             if (m >= 0 && m < S) o[m] = r[j].x * inv;
         }
-        PR_STAMP(6);
     }
 }
-#undef PR_STAMP
 
-template <bool G, bool D = false, bool P = false, bool POLAR = true>
+// (the last argument is unused and always null: it keeps the argument block's layout)
+template <bool G, bool D = false, bool POLAR = true>
 __global__ __launch_bounds__(PR_T) void k_fe_pairs8k(
     const float2* __restrict__ analytic, int n_slots, int N_, int pad_left_, int n_pairs, int B,
     const int* __restrict__ slot_i, const int* __restrict__ slot_j, const float* __restrict__ power,
     const float2* __restrict__ tab, const float* __restrict__ phi0, int start, int S, int pad_mode_,
-    float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+    float* __restrict__ out, unsigned long long* __restrict__) {
     const int N = G ? 4096 : N_;
     const int item = xcd_item(blockIdx.x, n_pairs * B);
     const int pair = item % n_pairs;
@@ -540,8 +525,7 @@ __global__ __launch_bounds__(PR_T) void k_fe_pairs8k(
     const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
     const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
     const float pw = power[pair];
-    fe_pairs8k_item<G, D, P, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, b, n_pairs, pair,
-                                    stamps);
+    fe_pairs8k_item<G, D, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, b, n_pairs, pair);
 }
 
 // Split sources (see k_fe_pairs_split): rows = B * K, row r = item / n_pairs.
@@ -558,8 +542,8 @@ __global__ __launch_bounds__(PR_T) void k_fe_pairs8k_split(
     const float2* ai = analytic_i + ((r / K) * n_slots_i + slot_i[pair]) * (int64_t)N;
     const float2* aj = analytic_j + (r * n_slots_j + slot_j[pair]) * (int64_t)N;
     const float pw = power[pair];
-    fe_pairs8k_item<G, false, false, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, r,
-                                            n_pairs, pair, nullptr);
+    fe_pairs8k_item<G, false, POLAR>(ai, aj, out, pw, N_, pad_left_, tab, phi0, start, S, pad_mode_, r, n_pairs,
+                                     pair);
 }
 
 // Persistent form of k_fe_pairs8k<true> (the training geometry): a grid of 2 workgroups per CU,
@@ -706,23 +690,18 @@ __global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
 //           product) while the other parity's d[] waits in registers.
 //   pass 2  each radix-16 job (block, n1a) split over two waves by output parity (the
 //           same radix-2 step, then a DFT-8); the pair reads before a barrier, writes after.
-//   pass 3  each (block, k'b) row summed by four lanes, 8 terms each, both outputs
-//           k'a = 0, 1 at once, the partials combined by DPP.
+//   pass 3  each (block, k'b) row summed by one lane of waves 0-1, both outputs k'a = 0, 1
+//           at once.
 // Another DFT-16 factorisation and summation order than k_fe_pairs8k (other rounding);
 // held to the same fp64 oracle (kymatio_phase_scattering.py:211-218, :233-273, :275-360).
 static constexpr int PRH_IMG = 8 * 528;                           // one parity's 8 blocks, 33-padded
 static constexpr int PRH_BUF = PRH_IMG > 4096 ? PRH_IMG : 4096;  // ... aliasing the staged product
 static constexpr int PRH_LDS = (PRH_BUF + PR_ZP) * (int)sizeof(float2);
+// waves per SIMD the registers are fitted to: three workgroups per CU at 80 VGPRs (four at 64
+// VGPRs spilled and were slower)
+static constexpr int PRH_OCC = 6;
 
 __device__ __forceinline__ c2 w16c(int n) { return w32(2 * n); }  // W_16^n (n a compile-time constant)
-
-// quad butterflies by DPP: lane l receives lane l ^ 1 / l ^ 2 of its quad
-__device__ __forceinline__ float qx1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float qx2(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-}
 
 // reflect-padded source index of column n1 = t, row n2 (training geometry: one reflection)
 __device__ __forceinline__ int prh_src(int t, int n2) {
@@ -735,23 +714,17 @@ __device__ __forceinline__ int prh_src(int t, int n2) {
 // 512 outputs X[k2 + 16 k'b + 256 k'a] (k'a < 2) in Z (conj(X phi), as k_fe_pairs8k).  Enters
 // with img free, leaves with pass 3's reads of img possibly still in flight in waves 0-1 (the
 // caller's barrier).
-// P3: pass-3 form (1: one lane per row on waves 0-1, the default; 0: four lanes per row).  Measured
-// and dropped: pass 2 as one thread per radix-16 job on waves 0-3 (no pair split, no middle barrier,
+// Measured and dropped: pass 3 as four lanes per row, the partials combined by DPP (0.704 vs 0.677
+// ms per launch); pass 2 as one thread per radix-16 job on waves 0-3 (no pair split, no middle barrier,
 // fewer VALU): 0.78 vs 0.67 ms per launch in the step — four waves cannot hide its 16 LDS reads.
-template <int H, int OCC, int P3>
+template <int H>
 __device__ __forceinline__ void prh_parity(float2* img, float2* Z, const c2 (&y)[8],
                                            const float2* __restrict__ tab, const float* __restrict__ phi0) {
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     // phi at this lane's pass-3 outputs (loaded ahead, consumed after two barriers)
-    float ph, ph1 = 0.f;
-    if constexpr (P3 == 1) {
-        const int k3 = (2 * (t >> 4) + H) + 16 * (t & 15);
-        ph = t < 128 ? phi0[k3] : 0.f;
-        ph1 = t < 128 ? phi0[k3 + 256] : 0.f;
-    } else {
-        ph = phi0[(2 * (t >> 6) + H) + 16 * ((t >> 2) & 15) + 256 * (t & 1)];
-    }
+    const int k3p = (2 * (t >> 4) + H) + 16 * (t & 15);
+    const float ph = t < 128 ? phi0[k3p] : 0.f, ph1 = t < 128 ? phi0[k3p + 256] : 0.f;
 #pragma unroll
     for (int m = 0; m < 8; ++m) img[528 * m + pr_pos(t)] = F2(y[m]);
     {
@@ -766,9 +739,8 @@ __device__ __forceinline__ void prh_parity(float2* img, float2* Z, const c2 (&y)
                 if (kb > 0) tw[q] = C2(tab[TW8K_T2 + 32 * (kb - 1) + n1a]);
             }
         };
-        if constexpr (OCC == 6) load_tw();   // in flight across the barrier (at 8 waves / SIMD: after it, registers)
+        load_tw();   // in flight across the barrier
         __syncthreads();
-        if constexpr (OCC != 6) load_tw();
         c2 x[8];
         if (p2 == 0) {
 #pragma unroll
@@ -792,57 +764,29 @@ __device__ __forceinline__ void prh_parity(float2* img, float2* Z, const c2 (&y)
         }
     }
     __syncthreads();
-    if constexpr (P3 == 1) {
-        // pass 3: one lane per row (block m = t >> 4, k'b = t & 15), waves 0-1 only (the kernel is
-        // issue bound: idle waves cost nothing, a row's work split over lanes costs the combine).
-        // The two outputs of the 32-point DFT over n1a by two radix-2 folds:
-        //   X0 = sum_n x_n,  X1 = sum_{n<8} ((x_n - x_{n+16}) - i (x_{n+8} - x_{n+24})) W_32^n
-        if (t < 128) {
-            const int m3 = t >> 4, kb3 = t & 15;
-            const float2* row = img + 528 * m3 + 33 * kb3;
-            c2 x0 = c2{0.f, 0.f}, x1 = c2{0.f, 0.f};
+    // pass 3: one lane per row (block m = t >> 4, k'b = t & 15), waves 0-1 only (the kernel is
+    // issue bound: idle waves cost nothing, a row's work split over lanes costs the combine).
+    // The two outputs of the 32-point DFT over n1a by two radix-2 folds:
+    //   X0 = sum_n x_n,  X1 = sum_{n<8} ((x_n - x_{n+16}) - i (x_{n+8} - x_{n+24})) W_32^n
+    if (t < 128) {
+        const int m3 = t >> 4, kb3 = t & 15;
+        const float2* row = img + 528 * m3 + 33 * kb3;
+        c2 x0 = c2{0.f, 0.f}, x1 = c2{0.f, 0.f};
 #pragma unroll
-            for (int n = 0; n < 8; ++n) {
-                const c2 a = C2(row[n]), b = C2(row[n + 8]), c = C2(row[n + 16]), e = C2(row[n + 24]);
-                x0 += (a + c) + (b + e);
-                const c2 f = add_mi(a - c, b - e);
-                x1 = n == 0 ? f : pmac(x1, f, w32(n));
-            }
-            const int k3 = (2 * m3 + H) + 16 * kb3;
-            Z[z512_pos(k3)] = make_float2(x0.x * ph, -x0.y * ph);
-            Z[z512_pos(k3 + 256)] = make_float2(x1.x * ph1, -x1.y * ph1);
+        for (int n = 0; n < 8; ++n) {
+            const c2 a = C2(row[n]), b = C2(row[n + 8]), c = C2(row[n + 16]), e = C2(row[n + 24]);
+            x0 += (a + c) + (b + e);
+            const c2 f = add_mi(a - c, b - e);
+            x1 = n == 0 ? f : pmac(x1, f, w32(n));
         }
-    } else {
-        // pass 3: row (block m = wv, k'b = (t >> 2) & 15), quarter q3 = t & 3 (n1a = 8 q3 + j)
-        const int q3 = t & 3, kb3 = (t >> 2) & 15;
-        const float2* row = img + 528 * wv + 33 * kb3 + 8 * q3;
-        c2 e0 = C2(row[0]), e1 = e0;
-#pragma unroll
-        for (int j = 1; j < 8; ++j) {
-            const c2 v = C2(row[j]);
-            e0 += v;
-            e1 = pmac(e1, v, w32(j));                // W_32^j
-        }
-        // W_32^{8 q3} = (-i)^q3
-        float rx = (q3 & 1) ? e1.y : e1.x, ry = (q3 & 1) ? -e1.x : e1.y;
-        const float sg = (q3 & 2) ? -1.f : 1.f;
-        rx *= sg;
-        ry *= sg;
-        float a0 = e0.x + qx1(e0.x), a1 = e0.y + qx1(e0.y), b0 = rx + qx1(rx), b1 = ry + qx1(ry);
-        a0 += qx2(a0);
-        a1 += qx2(a1);
-        b0 += qx2(b0);
-        b1 += qx2(b1);
-        if (q3 < 2) {
-            const int k3 = (2 * wv + H) + 16 * kb3 + 256 * q3;
-            const float xr = q3 ? b0 : a0, xi = q3 ? b1 : a1;
-            Z[z512_pos(k3)] = make_float2(xr * ph, -xi * ph);
-        }
+        const int k3 = (2 * m3 + H) + 16 * kb3;
+        Z[z512_pos(k3)] = make_float2(x0.x * ph, -x0.y * ph);
+        Z[z512_pos(k3 + 256)] = make_float2(x1.x * ph1, -x1.y * ph1);
     }
 }
 
 // One (row, pair) item of the half-image form: ai / aj its two analytic signals, o its output row.
-template <bool POLAR, int OCC, int P3>
+template <bool POLAR>
 __device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2* aj, float* __restrict__ o,
                                                   const float pw, const float2* __restrict__ tab,
                                                   const float* __restrict__ phi0, int start, int S) {
@@ -851,7 +795,7 @@ __device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2
     float2* Z = sm + PRH_BUF;      // PR_ZP
     const int t = threadIdx.x;
     // 0: accelerated product c[u], u < N (kymatio_phase_scattering.py:211-218, :282-283)
-    constexpr int LB = OCC == 6 ? 8 : 4;   // loads in flight per batch
+    constexpr int LB = 8;   // loads in flight per batch
 #pragma unroll
     for (int k0 = 0; k0 < 8; k0 += LB) {
         float2 xa[LB], xb[LB];
@@ -881,7 +825,7 @@ __device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2
 #pragma unroll
     for (int m = 1; m < 8; ++m) s[m] = pmul(s[m], w[m]);
     __syncthreads();   // the product is consumed: the image overwrites it
-    prh_parity<0, OCC, P3>(img, Z, s, tab, phi0);
+    prh_parity<0>(img, Z, s, tab, phi0);
     // pass 1 of the odd blocks in registers: waves 2-7 run it while waves 0-1 finish pass 3
 #pragma unroll
     for (int m = 0; m < 8; ++m) w[m] = C2(tab[TW8K_T1 + 512 * (2 * m) + t]);       // W_8192^{t (2m + 1)}
@@ -889,7 +833,7 @@ __device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2
 #pragma unroll
     for (int m = 0; m < 8; ++m) d[m] = pmul(d[m], w[m]);
     __syncthreads();   // the even blocks' pass 3 has read the image
-    prh_parity<1, OCC, P3>(img, Z, d, tab, phi0);
+    prh_parity<1>(img, Z, d, tab, phi0);
     c2 w5[7], wb5[7];
     if (t < 64) fft512_twiddles(tab, w5, wb5);
     __syncthreads();
@@ -907,9 +851,8 @@ __device__ __forceinline__ void fe_pairs8k_h_item(const float2* ai, const float2
     }
 }
 
-// OCC: waves per SIMD the registers are fitted to (6: three workgroups per CU, 80 VGPRs; 8: four, 64)
-template <bool POLAR, int OCC, int P3 = 1>
-__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_fe_pairs8k_h(
+template <bool POLAR>
+__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(PRH_OCC, PRH_OCC))) void k_fe_pairs8k_h(
     const float2* __restrict__ analytic, int n_slots, int n_pairs, int B, const int* __restrict__ slot_i,
     const int* __restrict__ slot_j, const float* __restrict__ power, const float2* __restrict__ tab,
     const float* __restrict__ phi0, int start, int S, float* __restrict__ out) {
@@ -920,12 +863,12 @@ __global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))
     const float2* ai = analytic + (b * n_slots + slot_i[pair]) * (int64_t)N;
     const float2* aj = analytic + (b * n_slots + slot_j[pair]) * (int64_t)N;
     const float pw = power[pair];
-    fe_pairs8k_h_item<POLAR, OCC, P3>(ai, aj, out + (b * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
+    fe_pairs8k_h_item<POLAR>(ai, aj, out + (b * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
 }
 
 // Split sources (see k_fe_pairs_split): rows = B * K, row r = item / n_pairs.
-template <bool POLAR, int OCC, int P3 = 1>
-__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_fe_pairs8k_h_split(
+template <bool POLAR>
+__global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(PRH_OCC, PRH_OCC))) void k_fe_pairs8k_h_split(
     const float2* __restrict__ analytic_i, int n_slots_i, const float2* __restrict__ analytic_j, int n_slots_j, int K,
     int n_pairs, int rows, const int* __restrict__ slot_i, const int* __restrict__ slot_j,
     const float* __restrict__ power, const float2* __restrict__ tab, const float* __restrict__ phi0, int start,
@@ -937,7 +880,7 @@ __global__ __launch_bounds__(PR_T) __attribute__((amdgpu_waves_per_eu(OCC, OCC))
     const float2* ai = analytic_i + ((r / K) * n_slots_i + slot_i[pair]) * (int64_t)N;
     const float2* aj = analytic_j + (r * n_slots_j + slot_j[pair]) * (int64_t)N;
     const float pw = power[pair];
-    fe_pairs8k_h_item<POLAR, OCC, P3>(ai, aj, out + (r * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
+    fe_pairs8k_h_item<POLAR>(ai, aj, out + (r * n_pairs + pair) * (int64_t)S, pw, tab, phi0, start, S);
 }
 
 // ------------------------------------------- wavelets, 8192-point register FFT
@@ -1378,11 +1321,10 @@ int vt_fe_wavelet(const void* xhat, int64_t B, int C, int n_pad, const float* ps
         const float2* tab = tw8k_tables(S(stream));
         VT_CHECK_ARG(tab != nullptr, "vt_fe_wavelet: twiddle tables unavailable (first call under stream capture?)");
         VT_CHECK_ARG((int64_t)n_items * B < (1ll << 31), "vt_fe_wavelet: grid");
-        // VAETEB_WAVELET_LP=0: the S1 low-pass with a global h0 load and a square root per tap (A/B)
+        // radius >= 2048: the S1 low-pass with a global h0 load and a square root per tap
         // (two threads per output with the taps summed in two halves: 411 -> 380 us, but other
         // bits, and the J = 6 end-to-end gradient bound failed on them: not kept)
-        static const bool lp_env = !(getenv("VAETEB_WAVELET_LP") && getenv("VAETEB_WAVELET_LP")[0] == '0');
-        const bool lp = lp_env && radius < 2048;
+        const bool lp = radius < 2048;
         const bool pol = analytic_polar(n_pad, N, pad_left);
         auto kern = pol ? (lp ? k_fe_wavelet8k<true, true> : k_fe_wavelet8k<true, false>)
                         : (lp ? k_fe_wavelet8k<false, true> : k_fe_wavelet8k<false, false>);
@@ -1399,7 +1341,6 @@ int vt_fe_wavelet(const void* xhat, int64_t B, int C, int n_pad, const float* ps
     return VT_OK;
 }
 
-static unsigned long long* g_pairs_stamps = nullptr;  // diagnostic phase stamps (nullptr: off)
 // persistent pair kernel grid (k_fe_pairs8k_p): VAETEB_PAIRS_PERSIST workgroups (a multiple of 8;
 // -1: 2 per CU).  Default 0 = the one-item-per-workgroup kernel: measured in the bench step,
 // the persistent form is slower (0.932 vs 0.844 ms per launch, round 4) — bit-identical, kept
@@ -1447,14 +1388,14 @@ static int g_pairs_half = -1;
 static int pairs_half() {
     if (g_pairs_half < 0) {
         const char* e = getenv("VAETEB_PAIRS_HALF");
-        g_pairs_half = e != nullptr ? atoi(e) : 1;
+        g_pairs_half = e != nullptr ? atoi(e) > 0 : 1;
     }
     return g_pairs_half;
 }
 
 int vt_fe_set_pairs_half(int on) {
     const int prev = pairs_half();
-    g_pairs_half = on < 0 ? 0 : on;   // 2: the 64-VGPR form (four workgroups per CU)
+    g_pairs_half = on > 0;
     return prev;
 }
 
@@ -1462,14 +1403,6 @@ int vt_fe_set_pairs_direct(int on) {
     const int prev = pairs_direct();
     g_pairs_direct = on ? 1 : 0;
     return prev;
-}
-
-// Diagnostic: stamp the phase boundaries of the training-geometry pair kernel
-// (LDS-staged variant) into buf, 8 uint64 per (sample, pair), successive launches
-// one after the other; nullptr turns it off.
-int vt_fe_set_pairs_stamps(void* buf) {
-    g_pairs_stamps = (unsigned long long*)buf;
-    return VT_OK;
 }
 
 int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, int pad_left, int n_pairs,
@@ -1487,18 +1420,16 @@ int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, 
         // and the doubled L2 reads compete (1.19 -> 1.32 ms per launch): opt-in
         const bool direct = pairs_direct() != 0;
         const bool pol = analytic_polar(n_pad, N, pad_left);
-        auto kern = pol ? (geo ? (direct ? k_fe_pairs8k<true, true, false, true> : k_fe_pairs8k<true, false, false, true>)
-                               : k_fe_pairs8k<false, false, false, true>)
-                        : (geo ? (direct ? k_fe_pairs8k<true, true, false, false> : k_fe_pairs8k<true, false, false, false>)
-                               : k_fe_pairs8k<false, false, false, false>);
-        if (g_pairs_stamps != nullptr && geo && !direct)
-            kern = pol ? k_fe_pairs8k<true, false, true, true> : k_fe_pairs8k<true, false, true, false>;
+        auto kern = pol ? (geo ? (direct ? k_fe_pairs8k<true, true, true> : k_fe_pairs8k<true, false, true>)
+                               : k_fe_pairs8k<false, false, true>)
+                        : (geo ? (direct ? k_fe_pairs8k<true, true, false> : k_fe_pairs8k<true, false, false>)
+                               : k_fe_pairs8k<false, false, false>);
         const float2* tab = tw8k_tables(S(stream));
         VT_CHECK_ARG(tab != nullptr, "vt_fe_pairs: twiddle tables unavailable (first call under stream capture?)");
         VT_CHECK_ARG((int64_t)n_pairs * B < (1ll << 31), "vt_fe_pairs: grid");
         const int64_t total = (int64_t)n_pairs * B;
         const int pgrid = pairs_persist_grid();
-        if (geo && !direct && g_pairs_stamps == nullptr && pgrid > 0 && total >= 2 * pgrid) {
+        if (geo && !direct && pgrid > 0 && total >= 2 * pgrid) {
             hipLaunchKernelGGL(pol ? k_fe_pairs8k_p<true> : k_fe_pairs8k_p<false>, dim3((unsigned)pgrid), dim3(PR_T),
                                (PR_IMG + PR_ZP) * sizeof(float2),
                                S(stream), (const float2*)analytic, n_slots, n_pairs, (int)B, slot_i, slot_j, power, tab,
@@ -1506,16 +1437,8 @@ int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, 
             VT_LAUNCH_CHECK("vt_fe_pairs");
             return VT_OK;
         }
-        if (geo && !direct && g_pairs_stamps == nullptr && pairs_half()) {
-            // 1: 3 workgroups / CU; 2: 4 (64 VGPRs, spills: slower); 3: 3 with the four-lane pass 3
-            const int hf = pairs_half();
-            hipLaunchKernelGGL(pol ? (hf == 2   ? k_fe_pairs8k_h<true, 8>
-                                      : hf == 3 ? k_fe_pairs8k_h<true, 6, 0>
-                                                : k_fe_pairs8k_h<true, 6>)
-                                   : (hf == 2   ? k_fe_pairs8k_h<false, 8>
-                                      : hf == 3 ? k_fe_pairs8k_h<false, 6, 0>
-                                                : k_fe_pairs8k_h<false, 6>),
-                               dim3((unsigned)total), dim3(PR_T),
+        if (geo && !direct && pairs_half()) {
+            hipLaunchKernelGGL(pol ? k_fe_pairs8k_h<true> : k_fe_pairs8k_h<false>, dim3((unsigned)total), dim3(PR_T),
                                PRH_LDS, S(stream), (const float2*)analytic, n_slots, n_pairs, (int)B, slot_i, slot_j,
                                power, tab, phi0, start, S_out, out);
             VT_LAUNCH_CHECK("vt_fe_pairs");
@@ -1523,8 +1446,7 @@ int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, 
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)(n_pairs * B)), dim3(PR_T), (PR_IMG + PR_ZP) * sizeof(float2),
                            S(stream), (const float2*)analytic, n_slots, N, pad_left, n_pairs, (int)B, slot_i, slot_j,
-                           power, tab, phi0, start, S_out, pad_mode, out, g_pairs_stamps);
-        if (g_pairs_stamps != nullptr && geo && !direct) g_pairs_stamps += (size_t)B * n_pairs * 8;  // next launch after
+                           power, tab, phi0, start, S_out, pad_mode, out, (unsigned long long*)nullptr);
     } else {
         hipLaunchKernelGGL(analytic_polar(n_pad, N, pad_left) ? k_fe_pairs<true> : k_fe_pairs<false>,
                            dim3(n_pairs, (unsigned)B), dim3(FE_THREADS), fft_lds_bytes(n_pad), S(stream),
@@ -1539,7 +1461,7 @@ int vt_fe_pairs(const void* analytic, int64_t B, int n_slots, int N, int n_pad, 
 // geometry and settings, so a row's bits are those of vt_fe_pairs on the same two signals: the
 // half-image form on the training geometry (vt_fe_set_pairs_half), the full-image form when that is
 // off or the persistent form (the same bits) would be chosen, and for other 8192-padded geometries,
-// the generic kernel elsewhere.  The direct-column and stamping diagnostics have no split form.
+// the generic kernel elsewhere.  The direct-column diagnostic has no split form.
 int vt_fe_pairs_split(const void* analytic_i, int n_slots_i, const void* analytic_j, int n_slots_j, int64_t B, int K,
                       int N, int n_pad, int pad_left, int n_pairs, const int* slot_i, const int* slot_j,
                       const float* power, const void* tw, const float* phi0, int dec, int start, int S_out,
@@ -1564,14 +1486,8 @@ int vt_fe_pairs_split(const void* analytic_i, int n_slots_i, const void* analyti
         const int64_t total = rows * n_pairs;
         const int pgrid = pairs_persist_grid();
         const bool persist = pgrid > 0 && total >= 2 * pgrid;   // vt_fe_pairs would run k_fe_pairs8k<true>'s bits
-        const int hf = pairs_half();
-        if (geo && !persist && hf) {
-            hipLaunchKernelGGL(pol ? (hf == 2   ? k_fe_pairs8k_h_split<true, 8>
-                                      : hf == 3 ? k_fe_pairs8k_h_split<true, 6, 0>
-                                                : k_fe_pairs8k_h_split<true, 6>)
-                                   : (hf == 2   ? k_fe_pairs8k_h_split<false, 8>
-                                      : hf == 3 ? k_fe_pairs8k_h_split<false, 6, 0>
-                                                : k_fe_pairs8k_h_split<false, 6>),
+        if (geo && !persist && pairs_half()) {
+            hipLaunchKernelGGL(pol ? k_fe_pairs8k_h_split<true> : k_fe_pairs8k_h_split<false>,
                                dim3((unsigned)total), dim3(PR_T), PRH_LDS, S(stream), Ai, n_slots_i, Aj, n_slots_j, K,
                                n_pairs, (int)rows, slot_i, slot_j, power, tab, phi0, start, S_out, out);
         } else {

@@ -29,8 +29,6 @@
 // and from the pair / quad kernels either so or, on request per layer, as the chunk image's own
 // bf16 values [B S][4H] in its column order k' = 4 u + g (one 8-byte store per lane and step
 // instead of four strided 4-byte ones; half the bytes).
-#include <stdlib.h>
-
 #include "common.h"
 #include "lstm_cell.h"
 
@@ -40,6 +38,11 @@ namespace l16 {
 static constexpr int H = 64;
 static constexpr int G4 = 4 * H;
 static constexpr int TC = 16;   // steps per chunk
+// samples per workgroup: the 4 row groups of the MFMA tiles hold samples lg & (NS - 1), so the
+// lanes of groups 2, 3 repeat groups 0, 1 and only groups 0, 1 store.  Against 4 samples per
+// workgroup (every group its own sample): half the per-CU store traffic, twice the workgroups
+// (the layer pairs at 4: 8.57 vs 8.19 ms per step)
+static constexpr int NS = 2;
 
 // flags of the chained launches (k_lstm16_fwd4 / _bwd4): T x nch words per launch from a pool
 // (arrive_slots: launches on different streams never share them), and the bounded waits'
@@ -65,13 +68,6 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// DIAG & 2 (timing probe only): shader-clock stamps of lane 0 of every wave of workgroup 0
-// at three points of each step, vector-stored to dbg[(t * 4 + wave) * 3 + k]
-__device__ __forceinline__ void stamp(unsigned long long* dbg, int t, int k) {
-    const unsigned long long v = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) dbg[((int64_t)t * 4 + (threadIdx.x >> 6)) * 3 + k] = v;
-}
-
 __device__ __forceinline__ f16x8 to_f16(float4 a, float4 b) {
     return f16x8{(_Float16)a.x, (_Float16)a.y, (_Float16)a.z, (_Float16)a.w,
                  (_Float16)b.x, (_Float16)b.y, (_Float16)b.z, (_Float16)b.w};
@@ -93,10 +89,8 @@ __device__ __forceinline__ float gate_scale(int g) { return g == 2 ? 2.f * NL2E 
 // x [B, S, In] (In % 4 == 0, In <= 32 KX), w_ih [4H][In], w_hh [4H][H];
 // out_h / out_c [B, S, H], out_hprev [B, S, H] (HP only); gates [B, S, H, 4]: post-activation
 // (i, f, g~, o) of each unit contiguous (one 16-B store per lane and step; private to
-// vt_lstm16_layer_bwd).  NS samples per workgroup (4 or 2): the 4 row groups of the MFMA
-// tiles hold samples lg & (NS - 1) — with NS = 2 the lanes of groups 2, 3 repeat groups 0, 1
-// and only groups 0, 1 store (half the per-CU store traffic, twice the workgroups).
-template <int NS, int KX, bool HP, int DIAG = 0>
+// vt_lstm16_layer_bwd).  NS samples per workgroup.
+template <int KX, bool HP>
 __global__ __launch_bounds__(G4) void k_lstm16_fwd(const float* __restrict__ x, int In, const float* __restrict__ wih,
                                                    const float* __restrict__ bih, const float* __restrict__ whh,
                                                    const float* __restrict__ bhh, int B, int S,
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(G4) void k_lstm16_fwd(const float* __restrict__ x, 
     const int j = threadIdx.x, lane = j & 63, w = j >> 6, ln = lane & 15, lg = lane >> 4;
     const int u = 16 * w + ln;                 // this lane's unit; its sample is sl
     const int sl = lg & (NS - 1), sa = (ln >> 2) & (NS - 1);   // the A row's sample: sa
-    const bool wr = NS == 4 || lg < NS;        // the lanes that store
+    const bool wr = lg < NS;                   // the lanes that store
     const int b0 = blockIdx.x * NS;
     // output row base of (sample sl); lanes of samples past B compute the clamped sample's
     // values bit for bit (same inputs, same instructions) and store them unmasked
@@ -194,7 +188,6 @@ __global__ __launch_bounds__(G4) void k_lstm16_fwd(const float* __restrict__ x, 
         for (int i = 0; i < TC; ++i) {
             if (i >= n) continue;   // block-uniform
             const int t = t0 + i;
-            if constexpr ((DIAG & 2) != 0) stamp(reinterpret_cast<unsigned long long*>(out_hprev), t, 0);
             const _Float16* hp = &hs[i & 1][sa][8 * lg];
             const f16x8 a0 = *reinterpret_cast<const f16x8*>(hp);
             const f16x8 a1 = *reinterpret_cast<const f16x8*>(hp + 32);
@@ -207,24 +200,11 @@ __global__ __launch_bounds__(G4) void k_lstm16_fwd(const float* __restrict__ x, 
                 p[g] = mma16(a1, bh[g][1], p[g]);
             }
             const int r = i & 3;
-            float gi, gf, gg, go;
-            if constexpr ((DIAG & 16) != 0) {   // probe: no activations
-                gi = p[0][r] * 0.1f, gf = p[1][r] * 0.1f, gg = p[2][r] * 0.1f, go = p[3][r] * 0.1f;
-            } else {
-                gi = sg2(p[0][r]), gf = sg2(p[1][r]), gg = th2(p[2][r]), go = sg2(p[3][r]);
-            }
-            if constexpr ((DIAG & 2) != 0) {
-                asm volatile("" ::"v"(gi), "v"(gf), "v"(gg), "v"(go));
-                stamp(reinterpret_cast<unsigned long long*>(out_hprev), t, 1);
-            }
+            const float gi = sg2(p[0][r]), gf = sg2(p[1][r]), gg = th2(p[2][r]), go = sg2(p[3][r]);
             c = cell_fwd_c(c, gi, gf, gg);
-            const float hn = (DIAG & 16) ? go * c : go * th2(2.f * NL2E * c);
+            const float hn = go * th2(2.f * NL2E * c);
             hs[(i + 1) & 1][sl][u] = (_Float16)hn;
-            if constexpr ((DIAG & 2) != 0) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                stamp(reinterpret_cast<unsigned long long*>(out_hprev), t, 2);
-            }
-            if (!(DIAG & 3) && wr) {
+            if (wr) {
                 *reinterpret_cast<float4*>(gates + ((ob + t) * H + u) * 4) = make_float4(gi, gf, gg, go);
                 out_h[(ob + t) * H + u] = hn;
                 if constexpr (HP) out_hprev[(ob + t) * H + u] = hprev;
@@ -280,7 +260,7 @@ __device__ __forceinline__ void chain_wait(unsigned* flag, unsigned* err) {
     }
 }
 
-template <int NS, int KX, int ROLE, int CH = 0>
+template <int KX, int ROLE, int CH = 0>
 __device__ __forceinline__ void fwd2_role(int In, const float* __restrict__ wih, const float* __restrict__ bih,
                                           const float* __restrict__ whh, const float* __restrict__ bhh, int B, int S,
                                           float* __restrict__ out_h, float* __restrict__ out_c,
@@ -290,7 +270,7 @@ __device__ __forceinline__ void fwd2_role(int In, const float* __restrict__ wih,
     const int j = threadIdx.x & (G4 - 1), lane = j & 63, w = j >> 6, ln = lane & 15, lg = lane >> 4;
     const int u = 16 * w + ln;
     const int sl = lg & (NS - 1), sa = (ln >> 2) & (NS - 1);
-    const bool wr = NS == 4 || lg < NS;
+    const bool wr = lg < NS;
     const int b0 = (CH ? tile : (int)blockIdx.x) * NS;
     // producer's upper layer: h through the coherence point (the consumer may sit on another XCD)
     const __amdgpu_buffer_rsrc_t hrs = agent_rsrc(out_h, (int64_t)B * S * H * 4);
@@ -419,7 +399,7 @@ __device__ __forceinline__ void fwd2_role(int In, const float* __restrict__ wih,
 // x [B, S, In] (In % 4 == 0, In <= 32 KXA); layer A's outputs hA / cA / gA, layer B's (input
 // size H) hB / cB / gB, as k_lstm16_fwd's (no h_{t-1} output).  Dynamic LDS:
 // fwd2_stage_bytes(NS, S), A's input [NS][ceil16(S)][HX] in f16.
-template <int NS, int KXA>
+template <int KXA>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_fwd2(const float* __restrict__ x, int In,
                                                         const float* __restrict__ wihA, const float* __restrict__ bihA,
                                                         const float* __restrict__ whhA, const float* __restrict__ bhhA,
@@ -471,9 +451,9 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_fwd2(const float* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     if (threadIdx.x < G4)
-        fwd2_role<NS, KXA, 0>(In, wihA, bihA, whhA, bhhA, B, S, hA, cA, gA, hsA, ximg, himg);
+        fwd2_role<KXA, 0>(In, wihA, bihA, whhA, bhhA, B, S, hA, cA, gA, hsA, ximg, himg);
     else
-        fwd2_role<NS, 2, 1>(H, wihB, bihB, whhB, bhhB, B, S, hB, cB, gB, hsB, ximg, himg);
+        fwd2_role<2, 1>(H, wihB, bihB, whhB, bhhB, B, S, hB, cB, gB, hsB, ximg, himg);
 }
 
 // the four layers' parameters [w_ih, w_hh, b_ih, b_hh] x 4 (the Python flat list's order) and
@@ -485,7 +465,6 @@ struct Quad {
 
 // zero the recurrence images and the staged input image, then (stage) the tile's whole input
 // x [B, S, In] in f16 (k_lstm16_fwd2's prologue)
-template <int NS>
 __device__ __forceinline__ void fwd2_prologue(const float* __restrict__ x, int In, int B, int S, int b0, bool stage,
                                               _Float16 (*hsA)[NS][HS], _Float16 (*hsB)[NS][HS], _Float16* ximg) {
     const int nch = (S + TC - 1) / TC, rows = NS * nch * TC;
@@ -530,7 +509,7 @@ __device__ __forceinline__ void fwd2_prologue(const float* __restrict__ x, int I
 // consumer: its input, layer 1's h, staged chunk by chunk as published).  slot0: T x nch zeroed
 // words of g_chain_flags (left zero by the consumers).  Same arithmetic
 // per role as two k_lstm16_fwd2 launches: the same bits.
-template <int NS, int KXA>
+template <int KXA>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_fwd4(const float* __restrict__ x, int In, Quad q, int B, int S,
                                                         int T, unsigned slot0) {
     unsigned* flags = g_chain_flags + slot0;
@@ -541,21 +520,21 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_fwd4(const float* __restrict_
     extern __shared__ __attribute__((aligned(16))) _Float16 ximg[];
     const bool cons = (int)blockIdx.x >= T;
     const int tile = cons ? (int)blockIdx.x - T : (int)blockIdx.x;
-    fwd2_prologue<NS>(x, In, B, S, tile * NS, !cons, hsA, hsB, ximg);
+    fwd2_prologue(x, In, B, S, tile * NS, !cons, hsA, hsB, ximg);
     const bool A = threadIdx.x < G4;
     if (!cons) {
         if (A)
-            fwd2_role<NS, KXA, 0, 1>(In, q.p[0], q.p[2], q.p[1], q.p[3], B, S, q.o[0], q.o[1], q.o[2], hsA, ximg,
+            fwd2_role<KXA, 0, 1>(In, q.p[0], q.p[2], q.p[1], q.p[3], B, S, q.o[0], q.o[1], q.o[2], hsA, ximg,
                                      himg, tile, flags, err);
         else
-            fwd2_role<NS, 2, 1, 1>(H, q.p[4], q.p[6], q.p[5], q.p[7], B, S, q.o[3], q.o[4], q.o[5], hsB, ximg, himg,
+            fwd2_role<2, 1, 1>(H, q.p[4], q.p[6], q.p[5], q.p[7], B, S, q.o[3], q.o[4], q.o[5], hsB, ximg, himg,
                                    tile, flags, err);
     } else {
         if (A)
-            fwd2_role<NS, 2, 0, 2>(H, q.p[8], q.p[10], q.p[9], q.p[11], B, S, q.o[6], q.o[7], q.o[8], hsA, ximg,
+            fwd2_role<2, 0, 2>(H, q.p[8], q.p[10], q.p[9], q.p[11], B, S, q.o[6], q.o[7], q.o[8], hsA, ximg,
                                    himg, tile, flags, err, q.o[3]);
         else
-            fwd2_role<NS, 2, 1, 2>(H, q.p[12], q.p[14], q.p[13], q.p[15], B, S, q.o[9], q.o[10], q.o[11], hsB, ximg,
+            fwd2_role<2, 1, 2>(H, q.p[12], q.p[14], q.p[13], q.p[15], B, S, q.o[9], q.o[10], q.o[11], hsB, ximg,
                                    himg, tile, flags, err);
     }
 }
@@ -582,7 +561,7 @@ __device__ __forceinline__ void cell_bwd16(float dh, float gi, float gf, float g
 
 // NS samples per workgroup as in the forward.  The dX chunk GEMM's M-tiles hold RPS = 16 / NS
 // steps of each sample (row rho = RPS s + tl), TC NS / 16 tiles per chunk.
-template <int NS, int NTX, bool WD, int DIAG = 0>
+template <int NTX, bool WD>
 __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_out, const float* __restrict__ gates,
                                                    const float* __restrict__ cst, const float* __restrict__ whh,
                                                    const float* __restrict__ wih, int In, int B, int S,
@@ -593,7 +572,7 @@ __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_
     const int j = threadIdx.x, lane = j & 63, w = j >> 6, ln = lane & 15, lg = lane >> 4;
     const int u = 16 * w + ln;
     const int sl = lg & (NS - 1), sa = (ln >> 2) & (NS - 1);
-    const bool wr = NS == 4 || lg < NS;
+    const bool wr = lg < NS;
     constexpr int RPS = 16 / NS, MT = TC * NS / 16;
     const int b0 = blockIdx.x * NS;
     const int64_t ob = (int64_t)(b0 + sl < B ? b0 + sl : B - 1) * S;
@@ -678,7 +657,6 @@ __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_
             }
             if (i >= n) continue;   // block-uniform (first processed chunk only)
             const int t = t0 + i, k8 = i & 7;
-            if constexpr ((DIAG & 2) != 0) stamp(reinterpret_cast<unsigned long long*>(dx), t, 0);
             // dh_rec = dg_{t+1} W_hh: A rows are the 4 samples' dg at t + 1 (zero at t = S - 1);
             // all 8 A fragments read before the first MFMA
             const __bf16* ap = (i + 1 < TC) ? &dgs[cur][i + 1][sa][8 * lg] : &dgs[cur ^ 1][0][sa][8 * lg];
@@ -696,21 +674,13 @@ __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_
             __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             const float dh = cd[k8] + (a0[0] + a1[0]);
-            if constexpr ((DIAG & 2) != 0) {
-                asm volatile("" ::"v"(dh));
-                stamp(reinterpret_cast<unsigned long long*>(dx), t, 1);
-            }
             float v0, v1, v2, v3;
             // tanh(c_t) with lstm_cell.h's relative accuracy near 0 (dg_o is proportional to it;
             // it depends on loaded c only, off the recurrence chain)
             cell_bwd16(dh, cg[k8].x, cg[k8].y, cg[k8].z, cg[k8].w, ftanh(cc[k8 + 1]), cc[k8], dc, v0, v1, v2, v3);
             typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
             *reinterpret_cast<bf16x4*>(&dgs[cur][i][sl][4 * u]) = bf16x4{(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
-            if constexpr ((DIAG & 2) != 0) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                stamp(reinterpret_cast<unsigned long long*>(dx), t, 2);
-            }
-            if (WD && !(DIAG & 3) && wr) {
+            if (WD && wr) {
                 float* o = dgates + (ob + t) * G4 + u;
                 o[0] = v0;
                 o[H] = v1;
@@ -721,7 +691,7 @@ __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_
         }
         // the chunk's dX = dG W_ih as one burst of 32 MFMAs per column tile from the complete
         // image (spread over the steps beside the recurrence's MFMAs it cost more than it hid)
-        if (dxw && !(DIAG & 2)) {
+        if (dxw) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 ax[m] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -743,7 +713,7 @@ __global__ __launch_bounds__(G4) void k_lstm16_bwd(const float* __restrict__ dh_
 // CH (chained backward, k_lstm16_bwd4): 1 = the upper pair (layers 3, 2), whose lower role publishes
 // its dX chunk by chunk (sc1 stores, a wait, the chunk's flag); 2 = the lower pair (layers 1, 0),
 // whose upper role reads dh_out (= that dX) with sc1 loads, each chunk after its flag is up.
-template <int NS, int NTX, int ROLE, int CH = 0>
+template <int NTX, int ROLE, int CH = 0>
 __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, const float* __restrict__ gates,
                                           const float* __restrict__ cst, const float* __restrict__ whh,
                                           const float* __restrict__ wih, int In, int B, int S,
@@ -754,7 +724,7 @@ __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, cons
     const int j = threadIdx.x & (G4 - 1), lane = j & 63, w = j >> 6, ln = lane & 15, lg = lane >> 4;
     const int u = 16 * w + ln;
     const int sl = lg & (NS - 1), sa = (ln >> 2) & (NS - 1);
-    const bool wr = NS == 4 || lg < NS;
+    const bool wr = lg < NS;
     constexpr int RPS = 16 / NS, MT = TC * NS / 16;
     const int b0 = (CH ? tile : (int)blockIdx.x) * NS;
     const int nchk = (S + TC - 1) / TC;
@@ -904,7 +874,7 @@ __device__ __forceinline__ void bwd2_role(const float* __restrict__ dh_out, cons
 // dh_out [B, S, H] at layer l + 1's outputs; gatesU / cU from layer l + 1's forward, gatesL /
 // cL from layer l's; W_hh / W_ih of both; dgU / dgL [B, S, 4H] fp32, or the bf16 image where fmt's
 // bit is set (bit 0 dgL, bit 1 dgU); dx [B, S, InL] (layer l's input gradient; may be null)
-template <int NS, int NTXL>
+template <int NTXL>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd2(const float* __restrict__ dh_out,
                                                         const float* __restrict__ gatesU, const float* __restrict__ cU,
                                                         const float* __restrict__ whhU, const float* __restrict__ wihU,
@@ -923,9 +893,9 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd2(const float* __restrict_
     }
     lds_barrier();
     if (threadIdx.x < G4)
-        bwd2_role<NS, 4, 0>(dh_out, gatesU, cU, whhU, wihU, H, B, S, dgU, fmt & 2, nullptr, dgsU, dximg, wTU);
+        bwd2_role<4, 0>(dh_out, gatesU, cU, whhU, wihU, H, B, S, dgU, fmt & 2, nullptr, dgsU, dximg, wTU);
     else
-        bwd2_role<NS, NTXL, 1>(nullptr, gatesL, cL, whhL, wihL, InL, B, S, dgL, fmt & 1, dx, dgsL, dximg, wTL);
+        bwd2_role<NTXL, 1>(nullptr, gatesL, cL, whhL, wihL, InL, B, S, dgL, fmt & 1, dx, dgsL, dximg, wTL);
 }
 
 // four layers' backward in one launch: workgroups [0, T) run layers 3, 2 of tile b (the producer:
@@ -940,7 +910,7 @@ struct QuadB {
     const float* c[4];
     float* dg[4];
 };
-template <int NS, int NTXL>
+template <int NTXL>
 __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd4(const float* __restrict__ dh_out, QuadB q, int In0, int B,
                                                         int S, int T, float* __restrict__ dmid, float* __restrict__ dx,
                                                         unsigned slot0, int fmt) {
@@ -960,17 +930,17 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd4(const float* __restrict_
     const int tile = cons ? (int)blockIdx.x - T : (int)blockIdx.x;
     if (!cons) {
         if (threadIdx.x < G4)
-            bwd2_role<NS, 4, 0, 1>(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], H, B, S, q.dg[3], fmt & 8, nullptr, dgsU,
+            bwd2_role<4, 0, 1>(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], H, B, S, q.dg[3], fmt & 8, nullptr, dgsU,
                                    dximg, wTU, tile, flags, err);
         else
-            bwd2_role<NS, 4, 1, 1>(nullptr, q.gates[2], q.c[2], q.w_hh[2], q.w_ih[2], H, B, S, q.dg[2], fmt & 4, dmid, dgsL,
+            bwd2_role<4, 1, 1>(nullptr, q.gates[2], q.c[2], q.w_hh[2], q.w_ih[2], H, B, S, q.dg[2], fmt & 4, dmid, dgsL,
                                    dximg, wTL, tile, flags, err);
     } else {
         if (threadIdx.x < G4)
-            bwd2_role<NS, 4, 0, 2>(dmid, q.gates[1], q.c[1], q.w_hh[1], q.w_ih[1], H, B, S, q.dg[1], fmt & 2, nullptr, dgsU,
+            bwd2_role<4, 0, 2>(dmid, q.gates[1], q.c[1], q.w_hh[1], q.w_ih[1], H, B, S, q.dg[1], fmt & 2, nullptr, dgsU,
                                    dximg, wTU, tile, flags, err);
         else
-            bwd2_role<NS, NTXL, 1, 2>(nullptr, q.gates[0], q.c[0], q.w_hh[0], q.w_ih[0], In0, B, S, q.dg[0], fmt & 1, dx, dgsL,
+            bwd2_role<NTXL, 1, 2>(nullptr, q.gates[0], q.c[0], q.w_hh[0], q.w_ih[0], In0, B, S, q.dg[0], fmt & 1, dx, dgsL,
                                       dximg, wTL, tile, flags, err);
     }
 }
@@ -979,59 +949,6 @@ __global__ __launch_bounds__(2 * G4) void k_lstm16_bwd4(const float* __restrict_
 }  // namespace vt
 
 using namespace vt::l16;
-
-namespace {
-
-// samples per workgroup: VAETEB_L16_NS (2 or 4; default 2)
-static int l16_ns() {
-    static const int ns = getenv("VAETEB_L16_NS") ? atoi(getenv("VAETEB_L16_NS")) : 2;
-    return ns == 4 ? 4 : 2;
-}
-// samples per workgroup of the layer-pair kernels: VAETEB_L16_PAIR_NS (2 or 4; default 2)
-static int l16_pair_ns() {
-    static const int ns = getenv("VAETEB_L16_PAIR_NS") ? atoi(getenv("VAETEB_L16_PAIR_NS")) : 2;
-    return ns == 4 ? 4 : 2;
-}
-// timing probes only (outputs not valid): 1 no stores, 2 in-kernel stamps
-static int l16_diag() {
-    static const int d = getenv("VAETEB_L16_DIAG") ? atoi(getenv("VAETEB_L16_DIAG")) : 0;
-    return d == 1 || d == 2 ? d : 0;
-}
-
-template <int NS, int KX>
-static void fwd_launch(dim3 grid, hipStream_t st, const float* x, int In, const float* w_ih, const float* b_ih,
-                       const float* w_hh, const float* b_hh, int B, int seq, float* h, float* hp, float* c,
-                       float* gates) {
-#define VT_L16F(HP_, D_) \
-    hipLaunchKernelGGL((k_lstm16_fwd<NS, KX, HP_, D_>), grid, dim3(G4), 0, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, \
-                       h, hp, c, gates)
-    switch (l16_diag()) {
-        case 1: VT_L16F(false, 1); break;
-        case 2: VT_L16F(true, 2); break;
-        default:
-            if (hp) VT_L16F(true, 0);
-            else VT_L16F(false, 0);
-    }
-#undef VT_L16F
-}
-
-template <int NS, int NTX>
-static void bwd_launch(dim3 grid, hipStream_t st, const float* dh_out, const float* gates, const float* cst,
-                       const float* w_hh, const float* w_ih, int In, int B, int seq, float* dgates, float* dx) {
-#define VT_L16B(W_, D_)                                                                                            \
-    hipLaunchKernelGGL((k_lstm16_bwd<NS, NTX, W_, D_>), grid, dim3(G4), 0, st, dh_out, gates, cst, w_hh, w_ih, In, \
-                       B, seq, dgates, dx)
-    switch (l16_diag()) {
-        case 1: VT_L16B(true, 1); break;
-        case 2: VT_L16B(true, 2); break;
-        default:
-            if (dgates) VT_L16B(true, 0);
-            else VT_L16B(false, 0);
-    }
-#undef VT_L16B
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -1042,17 +959,19 @@ int vt_lstm16_layer_fwd(const float* x, int In, const float* w_ih, const float* 
     VT_CHECK_ARG(B > 0 && seq > 0 && In > 0 && In <= 64 && In % 4 == 0,
                  "vt_lstm16_layer_fwd: shape (input size %d: a multiple of 4, at most 64)", In);
     VT_CHECK_ARG(x && w_ih && b_ih && w_hh && b_hh && out_h && out_c && gates, "vt_lstm16_layer_fwd: null pointer");
-    VT_CHECK_ARG(l16_diag() != 2 || out_hprev, "vt_lstm16_layer_fwd: the stamp probe writes into out_hprev");
-    const int ns = l16_ns();
-    const dim3 grid((B + ns - 1) / ns);
+    const dim3 grid((B + NS - 1) / NS);
     hipStream_t st = vt::S(stream);
-    if (ns == 4) {
-        if (In <= 32) fwd_launch<4, 1>(grid, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, out_h, out_hprev, out_c, gates);
-        else fwd_launch<4, 2>(grid, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, out_h, out_hprev, out_c, gates);
+#define VT_L16F(KX_, HP_)                                                                                        \
+    hipLaunchKernelGGL((k_lstm16_fwd<KX_, HP_>), grid, dim3(G4), 0, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, \
+                       out_h, out_hprev, out_c, gates)
+    if (In <= 32) {
+        if (out_hprev) VT_L16F(1, true);
+        else VT_L16F(1, false);
     } else {
-        if (In <= 32) fwd_launch<2, 1>(grid, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, out_h, out_hprev, out_c, gates);
-        else fwd_launch<2, 2>(grid, st, x, In, w_ih, b_ih, w_hh, b_hh, B, seq, out_h, out_hprev, out_c, gates);
+        if (out_hprev) VT_L16F(2, true);
+        else VT_L16F(2, false);
     }
+#undef VT_L16F
     VT_LAUNCH_CHECK("vt_lstm16_layer_fwd");
     return VT_OK;
 }
@@ -1067,21 +986,15 @@ int vt_lstm16_pair_fwd(const float* x, int In, const float* w_ih0, const float* 
     VT_CHECK_ARG(x && w_ih0 && b_ih0 && w_hh0 && b_hh0 && w_ih1 && b_ih1 && w_hh1 && b_hh1 && h0 && c0 && gates0 &&
                      h1 && c1 && gates1,
                  "vt_lstm16_pair_fwd: null pointer");
-    const int ns = l16_pair_ns();
-    const int64_t lds = fwd2_stage_bytes(ns, seq);
+    const int64_t lds = fwd2_stage_bytes(NS, seq);
     VT_CHECK_ARG(lds <= L16_PAIR_STAGE_MAX, "vt_lstm16_pair_fwd: sequence length %d too long for the staged input", seq);
-    const dim3 grid((B + ns - 1) / ns);
+    const dim3 grid((B + NS - 1) / NS);
     hipStream_t st = vt::S(stream);
-#define VT_L16F2(NS_, KX_)                                                                                          \
-    hipLaunchKernelGGL((k_lstm16_fwd2<NS_, KX_>), grid, dim3(2 * G4), lds, st, x, In, w_ih0, b_ih0, w_hh0, b_hh0, \
+#define VT_L16F2(KX_)                                                                                        \
+    hipLaunchKernelGGL((k_lstm16_fwd2<KX_>), grid, dim3(2 * G4), lds, st, x, In, w_ih0, b_ih0, w_hh0, b_hh0, \
                        w_ih1, b_ih1, w_hh1, b_hh1, B, seq, h0, c0, gates0, h1, c1, gates1)
-    if (ns == 4) {
-        if (In <= 32) VT_L16F2(4, 1);
-        else VT_L16F2(4, 2);
-    } else {
-        if (In <= 32) VT_L16F2(2, 1);
-        else VT_L16F2(2, 2);
-    }
+    if (In <= 32) VT_L16F2(1);
+    else VT_L16F2(2);
 #undef VT_L16F2
     VT_LAUNCH_CHECK("vt_lstm16_pair_fwd");
     return VT_OK;
@@ -1101,13 +1014,13 @@ int vt_lstm16_pair_bwd(const float* dh_out, const float* gates1, const float* c1
                  "vt_lstm16_pair_bwd: dgates format %d (bit 0: dgates0, bit 1: dgates1; images 8-byte aligned)", dg_bf16);
     float* dg1 = static_cast<float*>(dgates1);
     float* dg0 = static_cast<float*>(dgates0);
-    const dim3 grid((B + 1) / 2);
+    const dim3 grid((B + NS - 1) / NS);
     hipStream_t st = vt::S(stream);
     if (In0 <= 32)
-        hipLaunchKernelGGL((k_lstm16_bwd2<2, 2>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
+        hipLaunchKernelGGL((k_lstm16_bwd2<2>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
                            c0, w_hh0, w_ih0, In0, B, seq, dg1, dg0, dx, dg_bf16);
     else
-        hipLaunchKernelGGL((k_lstm16_bwd2<2, 4>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
+        hipLaunchKernelGGL((k_lstm16_bwd2<4>), grid, dim3(2 * G4), 0, st, dh_out, gates1, c1, w_hh1, w_ih1, gates0,
                            c0, w_hh0, w_ih0, In0, B, seq, dg1, dg0, dx, dg_bf16);
     VT_LAUNCH_CHECK("vt_lstm16_pair_bwd");
     return VT_OK;
@@ -1115,11 +1028,10 @@ int vt_lstm16_pair_bwd(const float* dh_out, const float* gates1, const float* c1
 
 // the chained launches need T (workgroups per pair) a multiple of 8 — tile b's producer and
 // consumer then sit on the same XCD of the round-robin workgroup placement — and flags within the
-// pool; otherwise (or VAETEB_L16_CHAIN=0) the two pair launches run one after the other (the same
-// kernels' arithmetic: the same bits either way)
+// pool; otherwise the two pair launches run one after the other (the same kernels' arithmetic:
+// the same bits either way)
 static bool l16_chain_ok(int T, int seq) {
-    static const bool on = !getenv("VAETEB_L16_CHAIN") || atoi(getenv("VAETEB_L16_CHAIN")) != 0;
-    return on && T % 8 == 0 && (int64_t)T * ((seq + TC - 1) / TC) <= (int64_t)vt::ARRIVE_POOL / 8;
+    return T % 8 == 0 && (int64_t)T * ((seq + TC - 1) / TC) <= (int64_t)vt::ARRIVE_POOL / 8;
 }
 
 int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B, int seq, int hidden,
@@ -1137,8 +1049,8 @@ int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B
         VT_CHECK_ARG(outs[i], "vt_lstm16_quad_fwd: null output %d", i);
         q.o[i] = outs[i];
     }
-    const int ns = l16_pair_ns(), T = (B + ns - 1) / ns;
-    const int64_t lds = fwd2_stage_bytes(ns, seq);
+    const int T = (B + NS - 1) / NS;
+    const int64_t lds = fwd2_stage_bytes(NS, seq);
     VT_CHECK_ARG(lds <= L16_PAIR_STAGE_MAX, "vt_lstm16_quad_fwd: sequence length %d too long for the staged input", seq);
     if (!l16_chain_ok(T, seq)) {
         int rc = vt_lstm16_pair_fwd(x, In, q.p[0], q.p[2], q.p[1], q.p[3], q.p[4], q.p[6], q.p[5], q.p[7], B, seq, H,
@@ -1150,16 +1062,10 @@ int vt_lstm16_quad_fwd(const float* x, int In, const float* const* params, int B
     hipStream_t st = vt::S(stream);
     const unsigned slot0 = vt::arrive_slots((unsigned)(T * ((seq + TC - 1) / TC)), st);
     const dim3 grid(2 * T);
-#define VT_L16F4(NS_, KX_) \
-    hipLaunchKernelGGL((k_lstm16_fwd4<NS_, KX_>), grid, dim3(2 * G4), lds, st, x, In, q, B, seq, T, slot0)
-    if (ns == 4) {
-        if (In <= 32) VT_L16F4(4, 1);
-        else VT_L16F4(4, 2);
-    } else {
-        if (In <= 32) VT_L16F4(2, 1);
-        else VT_L16F4(2, 2);
-    }
-#undef VT_L16F4
+    if (In <= 32)
+        hipLaunchKernelGGL((k_lstm16_fwd4<1>), grid, dim3(2 * G4), lds, st, x, In, q, B, seq, T, slot0);
+    else
+        hipLaunchKernelGGL((k_lstm16_fwd4<2>), grid, dim3(2 * G4), lds, st, x, In, q, B, seq, T, slot0);
     VT_LAUNCH_CHECK("vt_lstm16_quad_fwd");
     return VT_OK;
 }
@@ -1183,7 +1089,7 @@ int vt_lstm16_quad_bwd(const float* dh_out, const float* const* w, const float* 
         VT_CHECK_ARG(q.w_hh[l] && q.gates[l] && q.c[l] && q.dg[l] && (q.w_ih[l] || (l == 0 && !dx)),
                      "vt_lstm16_quad_bwd: null pointer (layer %d)", l);
     }
-    const int T = (B + 1) / 2;
+    const int T = (B + NS - 1) / NS;
     if (!l16_chain_ok(T, seq)) {
         int rc = vt_lstm16_pair_bwd(dh_out, q.gates[3], q.c[3], q.w_hh[3], q.w_ih[3], q.gates[2], q.c[2], q.w_hh[2],
                                     q.w_ih[2], H, B, seq, H, q.dg[3], q.dg[2], dmid, stream, (dg_bf16 >> 2) & 3);
@@ -1194,10 +1100,10 @@ int vt_lstm16_quad_bwd(const float* dh_out, const float* const* w, const float* 
     hipStream_t st = vt::S(stream);
     const unsigned slot0 = vt::arrive_slots((unsigned)(T * ((seq + TC - 1) / TC)), st);
     if (In0 <= 32)
-        hipLaunchKernelGGL((k_lstm16_bwd4<2, 2>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
+        hipLaunchKernelGGL((k_lstm16_bwd4<2>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
                            dx, slot0, dg_bf16);
     else
-        hipLaunchKernelGGL((k_lstm16_bwd4<2, 4>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
+        hipLaunchKernelGGL((k_lstm16_bwd4<4>), dim3(2 * T), dim3(2 * G4), 0, st, dh_out, q, In0, B, seq, T, dmid,
                            dx, slot0, dg_bf16);
     VT_LAUNCH_CHECK("vt_lstm16_quad_bwd");
     return VT_OK;
@@ -1222,18 +1128,20 @@ int vt_lstm16_layer_bwd(const float* dh_out, const float* gates, const float* cs
     VT_CHECK_ARG(B > 0 && seq > 0 && In > 0 && In <= 64, "vt_lstm16_layer_bwd: shape (input size %d, at most 64)",
                  In);
     VT_CHECK_ARG(dh_out && gates && cst && w_hh && (w_ih || !dx), "vt_lstm16_layer_bwd: null pointer");
-    VT_CHECK_ARG(l16_diag() != 2 || dx, "vt_lstm16_layer_bwd: the stamp probe writes into dx");
-    const int ns = l16_ns();
-    const dim3 grid((B + ns - 1) / ns);
+    const dim3 grid((B + NS - 1) / NS);
     hipStream_t st = vt::S(stream);
+#define VT_L16B(NTX_, WD_)                                                                                      \
+    hipLaunchKernelGGL((k_lstm16_bwd<NTX_, WD_>), grid, dim3(G4), 0, st, dh_out, gates, cst, w_hh, w_ih, In, B, \
+                       seq, dgates, dx)
     // column tiles of dX: 2 cover In <= 32 (the encoders' first layers: 20 / 32), 4 the rest
-    if (ns == 4) {
-        if (In <= 32) bwd_launch<4, 2>(grid, st, dh_out, gates, cst, w_hh, w_ih, In, B, seq, dgates, dx);
-        else bwd_launch<4, 4>(grid, st, dh_out, gates, cst, w_hh, w_ih, In, B, seq, dgates, dx);
+    if (In <= 32) {
+        if (dgates) VT_L16B(2, true);
+        else VT_L16B(2, false);
     } else {
-        if (In <= 32) bwd_launch<2, 2>(grid, st, dh_out, gates, cst, w_hh, w_ih, In, B, seq, dgates, dx);
-        else bwd_launch<2, 4>(grid, st, dh_out, gates, cst, w_hh, w_ih, In, B, seq, dgates, dx);
+        if (dgates) VT_L16B(4, true);
+        else VT_L16B(4, false);
     }
+#undef VT_L16B
     VT_LAUNCH_CHECK("vt_lstm16_layer_bwd");
     return VT_OK;
 }

@@ -11,7 +11,6 @@
 // momentum 0.9, eps 1e-5) + ReLU/tanh for the conv blocks
 // (ref/model/vae_teb_model.py:175, :206-210, :230, :252-253).
 #include <math.h>
-#include <stdlib.h>
 
 #include "bnbwd.h"
 #include "common.h"
@@ -516,9 +515,10 @@ __global__ __launch_bounds__(NT) void k_bn_finalize(const float* __restrict__ pa
 // sums the group sums in group order and applies bn_fin_channel.  Fixed order throughout.
 constexpr int BN_GB = 64;
 VT_ARRIVE_POOL(g_arrive_bn);
-static int g_bn_fold = getenv("VAETEB_BN_FOLD") ? atoi(getenv("VAETEB_BN_FOLD")) : 1;
-static int g_bn_fold_blocks = getenv("VAETEB_BN_BLOCKS") ? atoi(getenv("VAETEB_BN_BLOCKS")) : 512;
-#define BN_FOLD_BLOCKS ((int64_t)(g_bn_fold_blocks > 0 && g_bn_fold_blocks <= 2048 ? g_bn_fold_blocks : 512))
+// column-partial blocks under the in-kernel finalize: at 2048 each block's arrival lengthened it
+// and the tails stacked over the block rounds (k_col_partial4 18.7 -> 40.6 us); at 512 time-neutral
+// against the separate finaliser (7.727-7.749 vs 7.749-7.767 ms per step), kept for the launch count
+constexpr int64_t BN_FOLD_BLOCKS = 512;
 
 __device__ __forceinline__ int bn_groups(int blocks) { return (blocks + BN_GB - 1) / BN_GB; }
 
@@ -759,7 +759,9 @@ __global__ __launch_bounds__(NT) void k_bn_dx4(const float* __restrict__ dy, con
 // r0 a multiple of 4: thread tid < T' reads the float4s at flat offsets
 // r0*C + 4 tid + 4T' k, 4T' a multiple of C, so its four channels never change;
 // the per-thread sums are combined in LDS in fixed order.
-template <int KIND, int ACT, bool DROP = false, int U = 4>
+// float4 of each stream in flight per thread (the sums do not depend on it)
+constexpr int COLP_U = 4;
+template <int KIND, int ACT, bool DROP = false>
 __global__ __launch_bounds__(NT) void k_col_partial4(const float* __restrict__ x, const float* __restrict__ dy,
                                                      int64_t M, int C, int64_t rows_per_block, int Tp,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -836,6 +838,7 @@ __global__ __launch_bounds__(NT) void k_col_partial4(const float* __restrict__ x
             else acc(e, v, g);
         };
         // U float4 of each stream in flight per thread (the same f sequence for any U: the same sums)
+        constexpr int U = COLP_U;
         int64_t f = r0 * C + 4 * tid;
         if constexpr (PIN) {
             for (; f + 4 * (U - 1) * (int64_t)Tp + 4 <= end; f += 4 * U * (int64_t)Tp) {
@@ -959,21 +962,10 @@ static void bn_dx_vec(const float* dy, const float* x, int64_t M, int C, const f
 #undef VT_F
 }
 
-// float4 of each stream in flight per thread of k_col_partial4 (VAETEB_COLP_U: 4 or 8; same bits)
-static int g_colp_u = getenv("VAETEB_COLP_U") ? atoi(getenv("VAETEB_COLP_U")) : 4;
-
 static void col_partial_vec(int kind, const float* x, const float* dy, int64_t M, int C, int64_t rpb, int blocks,
                             const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
                             float* part, hipStream_t st, BnFin fin, const DropArg* dr = nullptr) {
     const int Tp = colp_threads(C);
-    if (kind == 2 && !dr && g_colp_u == 8) {
-#define VT_F(A)                                                                                                    \
-        hipLaunchKernelGGL((k_col_partial4<2, A, false, 8>), dim3(blocks), dim3(NT), 0, st, x, dy, M, C, rpb, Tp,   \
-                           mean, rstd, gamma, beta, part, fin, DropArg{})
-        VT_ACT_SWITCH(act, VT_F)
-#undef VT_F
-        return;
-    }
     if (kind == 0) {
         hipLaunchKernelGGL((k_col_partial4<0, ACT_NONE>), dim3(blocks), dim3(NT), 0, st, x, dy, M, C, rpb, Tp, mean,
                            rstd, gamma, beta, part, fin, DropArg{});
@@ -1005,7 +997,7 @@ static BnFin no_fin() {
 static void col_partial_fin(int kind, const float* x, const float* dy, int64_t M, int C, int64_t rpb, int blocks,
                             const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
                             float* ws, hipStream_t st, BnFin f, const DropArg* dr = nullptr) {
-    if (C <= 128 && g_bn_fold) {
+    if (C <= 128) {
         const int ng = (blocks + BN_GB - 1) / BN_GB;
         f.gpart = reinterpret_cast<double*>(ws + (((int64_t)2 * C * blocks + 1) & ~(int64_t)1));
         f.slot0 = arrive_slots((unsigned)ng + 1, st);
@@ -1192,7 +1184,7 @@ static int bn_blocks(int64_t M, int64_t ws_floats, int C, int64_t* rpb) {
     int64_t blocks = (M + 255) / 256;
     // in-kernel finalize (C <= 128): fewer, longer blocks — every block's arrival (an atomic round
     // trip) lengthens it, and at 2048 blocks those waits stacked up over the block rounds
-    const int64_t cap = C <= 128 && g_bn_fold ? BN_FOLD_BLOCKS : 2048;
+    const int64_t cap = C <= 128 ? BN_FOLD_BLOCKS : 2048;
     if (blocks > cap) blocks = cap;
     while (blocks > 1 && need(blocks) > ws_floats) blocks = blocks * 15 / 16 < blocks - 1 ? blocks * 15 / 16 : blocks - 1;
     if (need(blocks) > ws_floats) return 0;

@@ -123,7 +123,7 @@ LSTM_GRAD_DEFER = int(os.environ.get("VAETEB_LSTM_GRAD_DEFER", "1"))
 # 16-bit LSTM layers two at a time (vt_lstm16_pair_fwd / _bwd: the upper layer one chunk
 # behind the lower in the same workgroup, bit-identical to the per-layer kernels)
 LSTM_PAIR = int(os.environ.get("VAETEB_L16_PAIR", "1"))
-_L16_PAIR_NS = 4 if os.environ.get("VAETEB_L16_PAIR_NS") == "4" else 2
+_L16_PAIR_NS = 2   # samples per workgroup of the pair kernels (lstm16.hip's NS)
 # 4-layer 16-bit LSTMs as ONE launch each way (vt_lstm16_quad_fwd / _bwd: the two layer pairs
 # concurrent, chained chunk by chunk through per-chunk flags; bit-identical to the pair launches)
 LSTM_CHAIN_FWD = int(os.environ.get("VAETEB_L16_CHAIN_FWD", "1"))
