@@ -649,6 +649,30 @@ int vt_conv1d_bwd_weight_bf16_in(const float* dY, const void* dY16, int dys, con
                                  const float* in_rstd, const float* in_gamma, const float* in_beta, int in_act, int B,
                                  int L_in, int Cin, int Cout, int K, int mode, int up, float* dW, int accumulate,
                                  float* ws, int64_t ws_floats, void* stream);
+/* Staged 16-bit hand-off between the blocks of a conv stack: a block's y = act(BN(conv)) is
+ * written once as the NEXT block's MFMA operand rows instead of in fp32 — (B, L_up, ceil8(C))
+ * elements of the current 16-bit format (vt_set_h16_format), L_up = 2 L when that block
+ * upsamples (the x2 linear interpolation of y applied, the fp32 values the conv kernels' window
+ * staging forms, rounded once), pad channels 0.  The consumer's forward and weight gradient copy
+ * those rows into their LDS windows as 16-byte segments (padding is an index mapping over
+ * them): the same operand bits as from the fp32 y, so bit-identical outputs, BatchNorm
+ * statistics and weight gradients.
+ * vt_batchnorm_apply_x16: the rows from a (B, L, C) pre-BN conv output and its statistics.
+ * vt_conv1d_bn_fwd_bf16_x16: vt_conv1d_bn_fwd_bf16 with exactly one of X (fp32) / X16 (staged
+ *   rows of this block's input, made for this block's `up`) and, Y16 non-NULL, this block's
+ *   output as staged rows for a next block whose `up` is y16_up (Y nullable: no fp32 output).
+ * vt_conv1d_bwd_weight_bf16_x16: vt_conv1d_bwd_weight_bf16_dy16s with the input as staged rows.
+ * replaces: ConvBlock -> ConvBlock in a Sequential (ref/model/vae_teb_model.py:175-212,
+ *           :230-253, the BatchNorm1d + activation output feeding the next Conv1d)         */
+int vt_batchnorm_apply_x16(const float* x, int B, int L, int C, const float* mean, const float* rstd,
+                           const float* gamma, const float* beta, int act, int up, void* y16, void* stream);
+int vt_conv1d_bn_fwd_bf16_x16(const float* X, const void* X16, int B, int L_in, int Cin, const void* w16, int Cout,
+                              int K, int mode, int up, const float* gamma, const float* beta, int act, float eps,
+                              float momentum, float* conv_out, float* Y, float* mean, float* rstd, float* run_mean,
+                              float* run_var, float* ws, int64_t ws_floats, void* Y16, int y16_up, void* stream);
+int vt_conv1d_bwd_weight_bf16_x16(const void* dY16, int dys, const void* X16, int B, int L_in, int Cin, int Cout,
+                                  int K, int mode, int up, float* dW, int accumulate, float* ws, int64_t ws_floats,
+                                  void* stream);
 /* Conv-block backward in two launches on a bf16 operand (conv_bwd16.hip):
  * vt_batchnorm_bwd_x16: the BatchNorm input gradient of vt_conv1d_bwd_gpad_bf16_bn (the
  *   same bits) written once, in bf16, rows of ceil32(C) channels (padding 0), from dY, the

@@ -4,6 +4,7 @@
 #pragma once
 #include "bnbwd.h"
 #include "common.h"
+#include "x16.h"
 
 namespace vt {
 
@@ -52,6 +53,16 @@ __device__ __forceinline__ float src_val(const float* __restrict__ xb, const Geo
 }
 
 
+// the x2 linear upsample's source rows of up-domain row t (0 <= t < 2 L_in): rows i0, i1 and the
+// weight l1 on i1 (every operation exact in fp32)
+__device__ __forceinline__ void up_rows(int t, int L_in, int& i0, int& i1, float& l1) {
+    float s = (t + 0.5f) * 0.5f - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    i0 = (int)s;
+    i1 = i0 + 1 < L_in ? i0 + 1 : L_in - 1;
+    l1 = s - (float)i0;
+}
+
 // Source row(s) of padded position tp, the per-row part of src_val: false for
 // a zero-padded position; else x row i0 (and i1 with weight l1 when
 // upsampling: value = (1 - l1) x[i0] + l1 x[i1], as src_val).
@@ -70,11 +81,7 @@ __device__ __forceinline__ bool src_row(const Geo& g, int tp, int& i0, int& i1, 
         l1 = 0.f;
         return true;
     }
-    float s = (t + 0.5f) * 0.5f - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i1 = i0 + 1 < g.L_in ? i0 + 1 : g.L_in - 1;
-    l1 = s - (float)i0;
+    up_rows(t, g.L_in, i0, i1, l1);
     return true;
 }
 
@@ -181,6 +188,19 @@ int sum_splits_launch(const float* part, int splits, int64_t n, float* out, int 
 // ibn (nullable): x is the previous block's pre-BN output, its BatchNorm + act applied in staging
 int cfw16_launch(const float* x, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st,
                  const BnIn* ibn = nullptr);
+// Staged 16-bit operand rows (the hand-off between the blocks of a conv stack): a block's
+// y = act(BN(conv)) written once as the NEXT block's MFMA operand — (B, L_up, ceil8(C)) elements
+// of the current 16-bit format, the x2 upsample already applied (the values src_vec forms, rounded
+// as the consumers' staging rounds them), pad channels 0.  A consumer sees them as a plain
+// non-upsampled input of L_up rows: its geometry is x16_geo and padding stays an index mapping.
+static inline Geo x16_geo(int B, int L_in, int Cin, int Cout, int K, int mode, int up) {
+    return geo(B, L_in * (up ? 2 : 1), Cin, Cout, K, mode, 0);
+}
+// conv_fwd16.hip: the flat forward on staged rows x16 (g = x16_geo); the position tile or VT_ERR_ARG
+int cfw16_x16_launch(const void* x16, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st);
+// norm.hip: the producer — x (B, L, C) pre-BN conv output -> out16 (B, L (x2 if up), ceil8(C))
+int bn_apply_x16_launch(const float* x, int B, int L, int C, const float* mean, const float* rstd,
+                        const float* gamma, const float* beta, int act, int up, void* out16, hipStream_t st);
 // conv_bf16.hip: the reflect mirror rows of a direct-dX backward-data conv added back (k_conv_fold_edges)
 void fold_edges_launch(float* dx, const float* edge, int B, int L, int pad, int C, hipStream_t st);
 int bn_apply_launch(const float* x, int64_t M, int C, const float* mean, const float* rstd, const float* gamma,

@@ -650,7 +650,8 @@ int vt_conv1d_bf16_shadow_batch(int n, const int64_t* W, const int* Cout, const 
 static int bn_fwd_bf16(const float* X, int B, int L_in, int Cin, const void* w16, int Cout, int K, int mode, int up,
                        const float* gamma, const float* beta, int act, float eps, float momentum, float* conv_out,
                        float* Y, float* mean, float* rstd, float* run_mean, float* run_var, float* ws,
-                       int64_t ws_floats, hipStream_t st, const BnIn* ibn, const char* who) {
+                       int64_t ws_floats, hipStream_t st, const BnIn* ibn, const char* who,
+                       const void* X16 = nullptr, void* Y16 = nullptr, int y16_up = 0) {
     VT_CHECK_ARG(B > 0 && L_in > 0 && Cin > 0 && Cout > 0 && K > 0 && K <= KMAXB && (mode == 0 || mode == 1),
                  "%s: shape (K <= %d)", who, KMAXB);
     Geo g = geo(B, L_in, Cin, Cout, K, mode, up);
@@ -658,11 +659,29 @@ static int bn_fwd_bf16(const float* X, int B, int L_in, int Cin, const void* w16
     const int TP = bf_launch(nullptr, g, nullptr, cin32, nullptr, g.L_out, nullptr, nullptr);
     const int tps = cdiv(g.L_out, TP);
     VT_CHECK_ARG(ws && ws_floats >= (int64_t)B * tps * 2 * Cout, "%s: workspace too small", who);
-    if (bf_launch(X, g, w16, cin32, conv_out, g.L_out, ws, st, nullptr, FoldOut{-1, 0, nullptr}, ibn) < 0) return VT_ERR_ARG;
+    if (X16) {
+        // the input as the previous block's staged 16-bit rows (upsample applied): the flat forward at
+        // every K, the same position tile, outputs and tile statistics as from the fp32 input
+        const int tp = cfw16_x16_launch(X16, x16_geo(B, L_in, Cin, Cout, K, mode, up), w16, conv_out, g.L_out, ws, st);
+        VT_CHECK_ARG(tp == TP, "%s: staged input rows (16-byte aligned, the window of %d channels in LDS)", who, Cin);
+    } else if (bf_launch(X, g, w16, cin32, conv_out, g.L_out, ws, st, nullptr, FoldOut{-1, 0, nullptr}, ibn) < 0)
+        return VT_ERR_ARG;
     bn_stats_finalize_launch(ws, tps, B, TP, g.L_out, Cout, eps, momentum, mean, rstd, run_mean, run_var, st);
     if (Y) bn_apply_launch(conv_out, (int64_t)B * g.L_out, Cout, mean, rstd, gamma, beta, act, Y, st);
+    if (Y16 && bn_apply_x16_launch(conv_out, B, g.L_out, Cout, mean, rstd, gamma, beta, act, y16_up, Y16, st))
+        return VT_ERR_ARG;
     VT_LAUNCH_CHECK(who);
     return VT_OK;
+}
+
+int vt_conv1d_bn_fwd_bf16_x16(const float* X, const void* X16, int B, int L_in, int Cin, const void* w16, int Cout,
+                              int K, int mode, int up, const float* gamma, const float* beta, int act, float eps,
+                              float momentum, float* conv_out, float* Y, float* mean, float* rstd, float* run_mean,
+                              float* run_var, float* ws, int64_t ws_floats, void* Y16, int y16_up, void* stream) {
+    VT_CHECK_ARG((X != nullptr) != (X16 != nullptr), "vt_conv1d_bn_fwd_bf16_x16: exactly one of X, X16");
+    return bn_fwd_bf16(X, B, L_in, Cin, w16, Cout, K, mode, up, gamma, beta, act, eps, momentum, conv_out, Y, mean,
+                       rstd, run_mean, run_var, ws, ws_floats, S(stream), nullptr, "vt_conv1d_bn_fwd_bf16_x16", X16,
+                       Y16, y16_up);
 }
 
 int vt_conv1d_bn_fwd_bf16(const float* X, int B, int L_in, int Cin, const void* w16, int Cout, int K, int mode,

@@ -210,14 +210,21 @@ constexpr int CDW_UF_WIDE = 12;   // ... for the 256-row chunks
 // CR: rows per chunk — 64 (DWR), or 256 for the narrow layers (dY <= 32 channels: four times
 // the MFMA work per staged chunk, the same k-step order, so the same bits)
 // IBN: as k_conv_dw_bf16 (the previous block's BatchNorm + act applied as the window is formed)
-template <int K, int PPW, int NWV, int CR = DWR, bool IBN = false, typename H = __bf16>
+// X16: the input is the previous block's staged 16-bit rows xh (conv.h x16_geo: g without upsample,
+// row stride xcs = ceil8(Cin), pad channels 0): the window image is their rows under the padding's
+// index mapping, prefetched and stored as 16-byte segments like dY — no F, no forming loop and
+// one barrier fewer per chunk; the same operand bits in the same order
+template <int K, int PPW, int NWV, int CR = DWR, bool IBN = false, typename H = __bf16, bool X16 = false>
 __global__ __launch_bounds__(64 * NWV) void k_cdw16(const H* __restrict__ dyb16, int dys,
                                                    const float* __restrict__ x, Geo g, int64_t rows_per_split,
                                                    int NTc, int npairs, int dstride, int xstride,
-                                                   float* __restrict__ part, int64_t total, BnIn bi, int ipo) {
+                                                   float* __restrict__ part, int64_t total, BnIn bi, int ipo,
+                                                   const H* __restrict__ xh, int xcs) {
+    static_assert(!(X16 && IBN), "k_cdw16: staged rows already carry the previous block's BatchNorm");
     constexpr int NT = 64 * NWV;
     constexpr int UD = CR == DWR ? CDW_UD * 256 / NT : CR * 4 / NT;   // CR 256: dY rows of <= 4 segments
-    constexpr int UF = CR == DWR ? CDW_UF * 256 / NT : CDW_UF_WIDE * 256 / NT;
+    constexpr int UF = X16 ? 1 : (CR == DWR ? CDW_UF * 256 / NT : CDW_UF_WIDE * 256 / NT);
+    constexpr int UX = X16 ? cdw16_x16_ux(CR, K, NT) : 1;   // window segments per thread and chunk
     extern __shared__ __attribute__((aligned(16))) char lb_raw[];
     H* const lb = reinterpret_cast<H*>(lb_raw);
     H* ds = lb;                          // [CR][dstride]   dY rows
@@ -249,6 +256,8 @@ __global__ __launch_bounds__(64 * NWV) void k_cdw16(const H* __restrict__ dyb16,
     // boundary at or below the source run)
     hv8<H> dv[UD];
     float4 fv[UF];
+    hv8<H> xv[UX];
+    const int osegs = cin16 / 8;
     struct Chunk {
         int b, t0, n, lo, hi, off, nv;
     };
@@ -268,6 +277,27 @@ __global__ __launch_bounds__(64 * NWV) void k_cdw16(const H* __restrict__ dyb16,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) dv[u][j] = (H)0.f;
             }
+        }
+        if constexpr (X16) {
+            // window rows t0 .. t0 + CR + K - 2 (zero past n + K - 1, outside the padding's rows and in
+            // the channel segments past xcs): clamped addresses, masked values
+            const H* xb = xh + (int64_t)c.b * g.L_in * xcs;
+#pragma unroll
+            for (int u = 0; u < UX; ++u) {
+                const int i = tid + NT * u;
+                const int t = i / osegs, o = i - t * osegs;
+                int i0 = 0, i1 = 0;
+                float l1 = 0.f;
+                const bool in = i < (CR + K - 1) * osegs && t < c.n + K - 1 && 8 * o < xcs &&
+                                src_row(g, c.t0 + t, i0, i1, l1);
+                xv[u] = *(const hv8<H>*)(xb + (int64_t)(in ? i0 : 0) * xcs + (in ? 8 * o : 0));
+                if (!in) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) xv[u][j] = (H)0.f;
+                }
+            }
+            c.lo = c.hi = c.off = c.nv = 0;
+            return;
         }
         src_span(g, c.t0, c.n + K - 1, c.lo, c.hi);
         const int64_t f0 = ((int64_t)c.b * g.L_in + c.lo) * g.Cin;
@@ -302,6 +332,16 @@ __global__ __launch_bounds__(64 * NWV) void k_cdw16(const H* __restrict__ dyb16,
                 *(hv8<H>*)(ds + t * dstride + 8 * sg) = dv[u];
             }
         }
+        if constexpr (X16) {
+#pragma unroll
+            for (int u = 0; u < UX; ++u) {
+                const int i = tid + NT * u;
+                if (i < (CR + K - 1) * osegs) {
+                    const int t = i / osegs, o = i - t * osegs;
+                    *(hv8<H>*)(xs + t * xstride + 8 * o) = xv[u];
+                }
+            }
+        } else {
 #pragma unroll
         for (int u = 0; u < UF; ++u)
             if (tid + NT * u < cur.nv) reinterpret_cast<float4*>(F)[tid + NT * u] = fv[u];
@@ -332,6 +372,7 @@ __global__ __launch_bounds__(64 * NWV) void k_cdw16(const H* __restrict__ dyb16,
                 }
                 *(hv8<H>*)(xs + t * xstride + cb) = v;
             }
+        }
         }
         __syncthreads();
         const int64_t rn = r + cur.n;
@@ -381,10 +422,11 @@ extern "C" {
 
 static int bwd_weight(const float* dY, const float* X, int B, int L_in, int Cin, int Cout, int K, int mode, int up,
                       float* dW, int accumulate, float* ws, int64_t ws_floats, hipStream_t st, const void* dy16,
-                      int dys = 0, const BnIn* ibn = nullptr) {
+                      int dys = 0, const BnIn* ibn = nullptr, const void* x16 = nullptr) {
     VT_CHECK_ARG(B > 0 && L_in > 0 && K > 0 && K <= KMAXB && Cin > 0 && Cout > 0 && Cin <= 128 && Cout <= 128,
                  "vt_conv1d_bwd_weight_bf16: shape (K <= %d, channels <= 128)", KMAXB);
-    Geo g = geo(B, L_in, Cin, Cout, K, mode, up);
+    // x16: the input as staged 16-bit rows (upsample applied) — the same rows, pairs and splits
+    Geo g = x16 ? x16_geo(B, L_in, Cin, Cout, K, mode, up) : geo(B, L_in, Cin, Cout, K, mode, up);
     const int NTc = cdiv(Cin, 16), npairs = cdiv(Cout, 16) * NTc;
     // pairs per wave: at most what the accumulators allow, and no more than the
     // 4 waves of one workgroup need (small layers: no MFMAs on empty pairs)
@@ -435,19 +477,44 @@ static int bwd_weight(const float* dY, const float* X, int B, int L_in, int Cin,
     const BnIn bi = ibn ? *ibn : BnIn{};
     const int ib = ibn ? 16 * (16 * cdiv(Cin, 16)) : 0;
     const int ipo_w = ((int)lds_wide + 15) & ~15, ipo_f = ((int)lds_flat + 15) & ~15, ipo_d = ((int)lds + 15) & ~15;
+    // staged input rows: the flat kernel at every K (x16.h: the window's segments in the per-thread
+    // prefetch, LDS without F), 256-row chunks under the fp32 path's condition on dY
+    const bool xwide = x16 && (g_conv_kern & 8) && cdiv(Cout, 16) <= 2 && cdw16_x16_fits(256, K, Cin) && rps >= 256;
+    const int xcs = x16_stride(Cin);
+    const size_t lds_xw = (size_t)cdw16_x16_lds(256, dstride, xstride), lds_x = (size_t)cdw16_x16_lds(DWR, dstride, xstride);
+    if (x16)
+        VT_CHECK_ARG(!ibn && dy16 && ((uintptr_t)x16 & 15) == 0 && ((uintptr_t)dy16 & 15) == 0 && dys % 8 == 0 &&
+                         cdw16_x16_fits(DWR, K, Cin) && (int64_t)(xwide ? lds_xw : lds_x) <= X16_LDS_MAX,
+                     "vt_conv1d_bwd_weight_bf16_x16: 16-byte aligned 16-bit dY16 / X16 rows required");
+#define VT_DWB_X16(HT, NW, CRR, LDSX)                                                                           \
+    hipLaunchKernelGGL((k_cdw16<KK, PP, NW, CRR, false, HT, true>), grid, dim3(64 * NW), LDSX, st,              \
+                       (const HT*)dy16, dys, nullptr, g, rps, NTc, npairs, dstride, xstride, ws, 0, BnIn{}, 0,  \
+                       (const HT*)x16, xcs)
 #define VT_DWB_ONE(IB, HT)                                                                                      \
-    if (wide && nwv == 8)                                                                                       \
+    if (xwide && nwv == 8)                                                                                      \
+        VT_DWB_X16(HT, 8, 256, lds_xw);                                                                         \
+    else if (xwide)                                                                                             \
+        VT_DWB_X16(HT, 4, 256, lds_xw);                                                                         \
+    else if (x16 && nwv == 8)                                                                                   \
+        VT_DWB_X16(HT, 8, DWR, lds_x);                                                                          \
+    else if (x16)                                                                                               \
+        VT_DWB_X16(HT, 4, DWR, lds_x);                                                                          \
+    else if (wide && nwv == 8)                                                                                  \
         hipLaunchKernelGGL((k_cdw16<KK, PP, 8, 256, IB, HT>), grid, dim3(512), ipo_w + ib, st, (const HT*)dy16,   \
-                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_w);             \
+                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_w,                  \
+                           (const HT*)nullptr, 0);                                                                 \
     else if (wide)                                                                                              \
         hipLaunchKernelGGL((k_cdw16<KK, PP, 4, 256, IB, HT>), grid, dim3(256), ipo_w + ib, st, (const HT*)dy16,   \
-                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_w);             \
+                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_w,                  \
+                           (const HT*)nullptr, 0);                                                                 \
     else if (flat && nwv == 8)                                                                                  \
         hipLaunchKernelGGL((k_cdw16<KK, PP, 8, DWR, IB, HT>), grid, dim3(512), ipo_f + ib, st, (const HT*)dy16,   \
-                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_f);             \
+                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_f,                  \
+                           (const HT*)nullptr, 0);                                                                 \
     else if (flat)                                                                                              \
         hipLaunchKernelGGL((k_cdw16<KK, PP, 4, DWR, IB, HT>), grid, dim3(256), ipo_f + ib, st, (const HT*)dy16,   \
-                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_f);             \
+                           dys, X, g, rps, NTc, npairs, dstride, xstride, ws, total_x, bi, ipo_f,                  \
+                           (const HT*)nullptr, 0);                                                                 \
     else if (dy16 && nwv == 8)                                                                                  \
         hipLaunchKernelGGL((k_conv_dw_bf16<KK, PP, true, 8, IB, HT>), grid, dim3(512), ipo_d + ib, st, dY, X, g,  \
                            rps, NTc, npairs, dstride, xstride, ws, (const HT*)dy16, dys, bi, ipo_d);           \
@@ -483,6 +550,7 @@ static int bwd_weight(const float* dY, const float* X, int B, int L_in, int Cin,
 #undef VT_DWB2
 #undef VT_DWB
 #undef VT_DWB_ONE
+#undef VT_DWB_X16
     const int rc = sum_splits_launch(ws, (int)splits, nout, dW, accumulate, st);
     if (rc) return rc;
     VT_LAUNCH_CHECK("vt_conv1d_bwd_weight_bf16");
@@ -508,6 +576,17 @@ int vt_conv1d_bwd_weight_bf16_dy16s(const void* dY16, int dys, const float* X, i
                  "vt_conv1d_bwd_weight_bf16_dy16s: null dY16 or row stride %d (a multiple of 8 >= ceil8(Cout))", dys);
     return bwd_weight(nullptr, X, B, L_in, Cin, Cout, K, mode, up, dW, accumulate, ws, ws_floats, S(stream),
                       dY16, dys);
+}
+
+// the weight gradient of a block whose input arrives as the previous block's staged 16-bit rows
+// X16 (vt_conv1d_bn_fwd_bf16_x16 / vt_batchnorm_apply_x16: (B, L_in (x2 if up), ceil8(Cin)))
+int vt_conv1d_bwd_weight_bf16_x16(const void* dY16, int dys, const void* X16, int B, int L_in, int Cin, int Cout,
+                                  int K, int mode, int up, float* dW, int accumulate, float* ws, int64_t ws_floats,
+                                  void* stream) {
+    VT_CHECK_ARG(dY16 != nullptr && X16 != nullptr && dys >= ((Cout + 7) & ~7) && dys % 8 == 0,
+                 "vt_conv1d_bwd_weight_bf16_x16: null dY16 / X16 or row stride %d (a multiple of 8 >= ceil8(Cout))", dys);
+    return bwd_weight(nullptr, nullptr, B, L_in, Cin, Cout, K, mode, up, dW, accumulate, ws, ws_floats, S(stream),
+                      dY16, dys, nullptr, X16);
 }
 
 // the weight gradient of a block whose input is the previous block's pre-BN conv output X

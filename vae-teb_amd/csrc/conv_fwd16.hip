@@ -35,10 +35,16 @@ struct FCfg {
 
 // IBN: x is the previous block's pre-BN conv output; its BatchNorm + activation (bi, staged
 // into LDS at byte ipo) are applied to the source samples as the window is formed
-template <int K, int NT, bool IBN = false, typename H = __bf16>
+// X16: the input is the previous block's staged 16-bit rows xh (conv.h x16_geo: g without
+// upsample, row stride xcs = ceil8(Cin), pad channels 0) — the window image is their rows under
+// the padding's index mapping, copied as 16-byte segments: no F, no forming pass and one barrier
+// fewer; the same operand bits, so the same outputs and statistics
+template <int K, int NT, bool IBN = false, typename H = __bf16, bool X16 = false>
 __global__ __launch_bounds__(256) void k_cfw16(const float* __restrict__ x, Geo g, int nch,
                                                const H* __restrict__ w16, float* __restrict__ y, int Lo,
-                                               float* __restrict__ stats, int64_t total, BnIn bi, int ipo) {
+                                               float* __restrict__ stats, int64_t total, BnIn bi, int ipo,
+                                               const H* __restrict__ xh, int xcs) {
+    static_assert(!(X16 && IBN), "k_cfw16: staged rows already carry the previous block's BatchNorm");
     using C = FCfg<K, NT>;
     constexpr int PM = C::PM, TC = C::TC, TP = C::TP, WIN = C::WIN;
     extern __shared__ __attribute__((aligned(16))) char lb_raw[];
@@ -64,6 +70,35 @@ __global__ __launch_bounds__(256) void k_cfw16(const float* __restrict__ x, Geo 
     load_taps(0);   // in flight during the window staging
     float* ip = reinterpret_cast<float*>(reinterpret_cast<char*>(lb) + ipo);
     if constexpr (IBN) stage_bn_in(bi, g.Cin, ip, cin32);   // visible after stage 1's barrier
+    if constexpr (X16) {
+        // window rows t0 .. t0 + WIN - 1 of every chunk straight from the staged rows: items of one
+        // row's 8-channel segment, U per thread in flight (clamped addresses, masked values)
+        const int segs = 4 * nch, xsegs = xcs >> 3;
+        const H* xb = xh + (int64_t)b * g.L_in * xcs;
+        constexpr int U = 4;
+        for (int j0 = tid; j0 < WIN * segs; j0 += 256 * U) {
+            hv8<H> v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = j0 + 256 * u;
+                const int r = i / segs, s = i - r * segs;
+                int i0 = 0, i1 = 0;
+                float l1 = 0.f;
+                const bool in = i < WIN * segs && t0 + r < Lo + K - 1 && s < xsegs && src_row(g, t0 + r, i0, i1, l1);
+                v[u] = *(const hv8<H>*)(xb + (int64_t)(in ? i0 : 0) * xcs + (in ? 8 * s : 0));
+                if (!in) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[u][j] = (H)0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = j0 + 256 * u;
+                const int r = i / segs, s = i - r * segs;
+                if (i < WIN * segs) *(hv8<H>*)(xs + ((s >> 2) * WIN + r) * RS + 8 * (s & 3)) = v[u];
+            }
+        }
+    } else {
     int lo, hi;
     src_span(g, t0, WIN < Lo + K - 1 - t0 ? WIN : Lo + K - 1 - t0, lo, hi);
     // 1. source rows lo .. hi: flat float4 copy (from the float4 boundary at or below the run)
@@ -126,6 +161,7 @@ __global__ __launch_bounds__(256) void k_cfw16(const float* __restrict__ x, Geo 
         }
     }
     __syncthreads();   // F is dead: the taps take its place
+    }
     auto store_taps = [&]() {
 #pragma unroll
         for (int it = 0; it < C::NWI; ++it) {
@@ -238,9 +274,22 @@ __global__ __launch_bounds__(256) void k_cfw16(const float* __restrict__ x, Geo 
 // source rows a window of WIN padded positions can read: WIN + 2 (x2 upsample: half, + 2)
 template <int K, int NT>
 int cfw_nt(const float* x, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st,
-           const BnIn* ibn) {
+           const BnIn* ibn, const void* x16) {
     using C = FCfg<K, NT>;
     const int nch = cdiv(g.Cin, 32);
+    if (x16) {   // staged 16-bit rows: the window and one chunk's taps in LDS (x16.h)
+        const int64_t lds = cfw16_x16_lds(K, NT, nch);
+        if (ibn || g.up || lds > X16_LDS_MAX || ((uintptr_t)x16 & 15)) return VT_ERR_ARG;
+        dim3 grid(cdiv(Lo, C::TP), cdiv(g.Cout, C::TC), g.B);
+        const int xcs = x16_stride(g.Cin);
+        if (h16_format())
+            hipLaunchKernelGGL((k_cfw16<K, NT, false, _Float16, true>), grid, dim3(256), (size_t)lds, st, nullptr, g, nch,
+                               (const _Float16*)w16, y, Lo, stats, 0, BnIn{}, 0, (const _Float16*)x16, xcs);
+        else
+            hipLaunchKernelGGL((k_cfw16<K, NT, false, __bf16, true>), grid, dim3(256), (size_t)lds, st, nullptr, g, nch,
+                               (const __bf16*)w16, y, Lo, stats, 0, BnIn{}, 0, (const __bf16*)x16, xcs);
+        return C::TP;
+    }
     const int src_rows = g.up ? C::WIN / 2 + 3 : C::WIN;
     const int fbytes = (src_rows * g.Cin + 8) * 4;
     const int rest = fbytes > C::WBYTES ? fbytes : C::WBYTES;
@@ -255,26 +304,43 @@ int cfw_nt(const float* x, const Geo& g, const void* w16, float* y, int Lo, floa
     if (h16_format()) {   // fp16 operands (h16.h); the conv-stack fold (ibn) is bf16-only
         if (ibn) return VT_ERR_ARG;
         hipLaunchKernelGGL((k_cfw16<K, NT, false, _Float16>), grid, dim3(256), lds, st, x, g, nch,
-                           (const _Float16*)w16, y, Lo, stats, total, bi, ipo);
+                           (const _Float16*)w16, y, Lo, stats, total, bi, ipo, nullptr, 0);
     } else if (ibn)
         hipLaunchKernelGGL((k_cfw16<K, NT, true, __bf16>), grid, dim3(256), lds, st, x, g, nch, (const __bf16*)w16, y, Lo, stats,
-                           total, bi, ipo);
+                           total, bi, ipo, nullptr, 0);
     else
         hipLaunchKernelGGL((k_cfw16<K, NT, false, __bf16>), grid, dim3(256), lds, st, x, g, nch, (const __bf16*)w16, y, Lo, stats,
-                           total, bi, ipo);
+                           total, bi, ipo, nullptr, 0);
     return C::TP;
 }
 
 template <int K>
 int cfw_k(const float* x, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st,
-          const BnIn* ibn) {
+          const BnIn* ibn, const void* x16) {
     switch (cdiv(g.Cout, 16) < 6 ? cdiv(g.Cout, 16) : 6) {
-        case 1: return cfw_nt<K, 1>(x, g, w16, y, Lo, stats, st, ibn);
-        case 2: return cfw_nt<K, 2>(x, g, w16, y, Lo, stats, st, ibn);
-        case 3: return cfw_nt<K, 3>(x, g, w16, y, Lo, stats, st, ibn);
-        case 4: return cfw_nt<K, 4>(x, g, w16, y, Lo, stats, st, ibn);
-        case 5: return cfw_nt<K, 5>(x, g, w16, y, Lo, stats, st, ibn);
-        default: return cfw_nt<K, 6>(x, g, w16, y, Lo, stats, st, ibn);
+        case 1: return cfw_nt<K, 1>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 2: return cfw_nt<K, 2>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 3: return cfw_nt<K, 3>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 4: return cfw_nt<K, 4>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 5: return cfw_nt<K, 5>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        default: return cfw_nt<K, 6>(x, g, w16, y, Lo, stats, st, ibn, x16);
+    }
+}
+
+int cfw16_any(const float* x, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st,
+              const BnIn* ibn, const void* x16) {
+    switch (g.K) {
+        case 1: return cfw_k<1>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 2: return cfw_k<2>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 3: return cfw_k<3>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 4: return cfw_k<4>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 5: return cfw_k<5>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 6: return cfw_k<6>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 7: return cfw_k<7>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 8: return cfw_k<8>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 9: return cfw_k<9>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        case 10: return cfw_k<10>(x, g, w16, y, Lo, stats, st, ibn, x16);
+        default: return cfw_k<11>(x, g, w16, y, Lo, stats, st, ibn, x16);
     }
 }
 
@@ -285,19 +351,11 @@ int cfw_k(const float* x, const Geo& g, const void* w16, float* y, int Lo, float
 // window's source rows do not fit in LDS (the caller uses k_conv_bf16)
 int cfw16_launch(const float* x, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st,
                  const BnIn* ibn) {
-    switch (g.K) {
-        case 1: return cfw_k<1>(x, g, w16, y, Lo, stats, st, ibn);
-        case 2: return cfw_k<2>(x, g, w16, y, Lo, stats, st, ibn);
-        case 3: return cfw_k<3>(x, g, w16, y, Lo, stats, st, ibn);
-        case 4: return cfw_k<4>(x, g, w16, y, Lo, stats, st, ibn);
-        case 5: return cfw_k<5>(x, g, w16, y, Lo, stats, st, ibn);
-        case 6: return cfw_k<6>(x, g, w16, y, Lo, stats, st, ibn);
-        case 7: return cfw_k<7>(x, g, w16, y, Lo, stats, st, ibn);
-        case 8: return cfw_k<8>(x, g, w16, y, Lo, stats, st, ibn);
-        case 9: return cfw_k<9>(x, g, w16, y, Lo, stats, st, ibn);
-        case 10: return cfw_k<10>(x, g, w16, y, Lo, stats, st, ibn);
-        default: return cfw_k<11>(x, g, w16, y, Lo, stats, st, ibn);
-    }
+    return cfw16_any(x, g, w16, y, Lo, stats, st, ibn, nullptr);
+}
+
+int cfw16_x16_launch(const void* x16, const Geo& g, const void* w16, float* y, int Lo, float* stats, hipStream_t st) {
+    return x16 ? cfw16_any(nullptr, g, w16, y, Lo, stats, st, nullptr, x16) : VT_ERR_ARG;
 }
 
 }  // namespace vt

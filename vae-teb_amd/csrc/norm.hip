@@ -14,7 +14,9 @@
 
 #include "bnbwd.h"
 #include "common.h"
+#include "conv.h"
 #include "dropout.h"
+#include "h16.h"
 
 namespace vt {
 
@@ -650,6 +652,107 @@ __global__ __launch_bounds__(NT) void k_bn_apply4(const float* __restrict__ x, i
     }
 }
 
+// The apply written as the next conv block's staged 16-bit operand rows (conv.h x16_geo): out row
+// (b, t) holds (H) of y = act(BN(x)) at row t, or with UP of the x2 linear upsample of y at
+// up-domain row t — up_lerp over the two source rows of conv.h up_rows, the fp32 value the
+// consumers' window staging forms from a materialised y — channel stride cs = ceil8(C), pad
+// channels 0.  A workgroup owns TR source rows of one sample (64, or 32 + one halo row with UP:
+// 64 output rows either way, 65 in a sample's first tile, x16.h): their floats are one contiguous run, read with float4 loads
+// from the 16-byte boundary at or below it and normalised on the way into LDS (y in fp32 with UP,
+// else straight into the 16-bit row image); with UP a second pass along the channels interpolates
+// the output rows into the row image; the rows leave as 16-byte segments.
+template <typename H, int ACT, bool UP>
+__global__ __launch_bounds__(NT) void k_bn_apply_x16(const float* __restrict__ x, int L, int C,
+                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     H* __restrict__ out, int cs, int64_t total) {
+    constexpr int TR = x16_apply_rows(UP);
+    extern __shared__ __attribute__((aligned(16))) float4 xl[];
+    float4* p = xl;                                    // [C] (mean, rstd, gamma, beta)
+    H* img = reinterpret_cast<H*>(xl + C);             // [65][cs] output rows (UP, first tile: 65)
+    float* yf = reinterpret_cast<float*>(img + X16_APPLY_OUT * cs);   // UP: [TR + 1][C] y
+    const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * TR;
+    for (int c = tid; c < C; c += NT) p[c] = make_float4(mean[c], rstd[c], gamma[c], beta[c]);
+    __syncthreads();
+    const int nrow = L - m0 < TR + (UP ? 1 : 0) ? L - m0 : TR + (UP ? 1 : 0);
+    const int n = nrow * C;
+    const int64_t f0 = ((int64_t)b * L + m0) * C, fa = f0 & ~(int64_t)3;
+    const int off = (int)(f0 - fa), nv = (off + n + 3) >> 2;
+    {
+        // element e = 4 i + j - off of the run: row r, channel c, advanced without divisions
+        const int e0 = 4 * tid - off + 4 * C;          // >= 0: four rows up
+        int r = e0 / C - 4, c = e0 % C;
+        const int rstep = (4 * NT) / C, cstep = (4 * NT) % C;
+        for (int i = tid; i < nv; i += NT) {
+            const int64_t g = fa + 4 * (int64_t)i;
+            float v[4];
+            if (g + 3 < total) {
+                const float4 f = *reinterpret_cast<const float4*>(x + g);
+                v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = g + j < total ? x[g + j] : 0.f;
+            }
+            int rr = r, cc = c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = 4 * i + j - off;
+                if (e >= 0 && e < n) {
+                    const float4 w = p[cc];
+                    const float y = bn_fwd_val(v[j], w.x, w.y, w.z, w.w, ACT);
+                    if constexpr (UP)
+                        yf[e] = y;
+                    else
+                        img[rr * cs + cc] = (H)y;
+                }
+                if (++cc == C) {
+                    cc = 0;
+                    ++rr;
+                }
+            }
+            r += rstep;
+            c += cstep;
+            if (c >= C) {
+                c -= C;
+                ++r;
+            }
+        }
+    }
+    __syncthreads();
+    // output rows t_lo .. t_lo + nt - 1 of the sample (UP: rows 2 m + 1, 2 m + 2 of source row m, and row 0)
+    const int Lx = UP ? 2 * L : L;
+    const int t_lo = UP ? (m0 == 0 ? 0 : 2 * m0 + 1) : m0;
+    const int t_end = UP ? (2 * (m0 + TR) + 1 < Lx ? 2 * (m0 + TR) + 1 : Lx) : (m0 + TR < L ? m0 + TR : L);
+    const int nt = t_end - t_lo;
+    if constexpr (UP) {
+        int r = tid / C, c = tid % C;
+        const int rstep = NT / C, cstep = NT % C;
+        for (int i = tid; i < nt * C; i += NT) {
+            int i0, i1;
+            float l1;
+            up_rows(t_lo + r, L, i0, i1, l1);
+            img[r * cs + c] = (H)up_lerp(yf[(i0 - m0) * C + c], yf[(i1 - m0) * C + c], l1);
+            r += rstep;
+            c += cstep;
+            if (c >= C) {
+                c -= C;
+                ++r;
+            }
+        }
+        __syncthreads();
+    }
+    // rows out as 16-byte segments, channels >= C zero
+    const int segs = cs >> 3;
+    for (int i = tid; i < nt * segs; i += NT) {
+        const int r = i / segs, sg = i - r * segs;
+        hv8<H> v = *reinterpret_cast<const hv8<H>*>(img + r * cs + 8 * sg);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (8 * sg + j >= C) v[j] = (H)0.f;
+        *reinterpret_cast<hv8<H>*>(out + ((int64_t)b * Lx + t_lo + r) * cs + 8 * sg) = v;
+    }
+}
+
 // Dropout1d of the BatchNorm backward's incoming gradient (vt_batchnorm_bwd_dropout): the
 // kernels read dy through dmask, i.e. the value cls.hip's k_dropout would have written
 struct DropArg {
@@ -1091,6 +1194,27 @@ int bn_apply_launch(const float* x, int64_t M, int C, const float* mean, const f
     return VT_OK;
 }
 
+int bn_apply_x16_launch(const float* x, int B, int L, int C, const float* mean, const float* rstd,
+                        const float* gamma, const float* beta, int act, int up, void* out16, hipStream_t st) {
+    if (!x16_apply_ok(B, L, C) || ((uintptr_t)out16 & 15) || ((uintptr_t)x & 15)) {
+        set_error("staged 16-bit rows: shape (B %d <= 65535, L %d, C %d <= %d) or a misaligned pointer", B, L, C,
+                  X16_CMAX);
+        return VT_ERR_ARG;
+    }
+    const int cs = x16_stride(C);
+    const dim3 grid((unsigned)((L + x16_apply_rows(up) - 1) / x16_apply_rows(up)), (unsigned)B);
+    const size_t lds = (size_t)x16_apply_lds(C, up);
+    const int64_t total = (int64_t)B * L * C;
+#define VT_F(A)                                                                                                   \
+    VT_H16(if (up) hipLaunchKernelGGL((k_bn_apply_x16<H, A, true>), grid, dim3(NT), lds, st, x, L, C, mean, rstd,  \
+                                      gamma, beta, (H*)out16, cs, total);                                        \
+           else hipLaunchKernelGGL((k_bn_apply_x16<H, A, false>), grid, dim3(NT), lds, st, x, L, C, mean, rstd,    \
+                                   gamma, beta, (H*)out16, cs, total))
+    VT_ACT_SWITCH(act, VT_F)
+#undef VT_F
+    return VT_OK;
+}
+
 }  // namespace vt
 
 using namespace vt;
@@ -1380,6 +1504,14 @@ int vt_batchnorm_apply(const float* x, int64_t M, int C, const float* mean, cons
     VT_CHECK_ARG(M > 0 && C > 0 && C <= BNV_C, "vt_batchnorm_apply: shape");
     bn_apply_vec(x, M, C, mean, rstd, gamma, beta, act, y, S(stream));
     VT_LAUNCH_CHECK("vt_batchnorm_apply");
+    return VT_OK;
+}
+
+int vt_batchnorm_apply_x16(const float* x, int B, int L, int C, const float* mean, const float* rstd,
+                           const float* gamma, const float* beta, int act, int up, void* y16, void* stream) {
+    VT_CHECK_ARG(x && mean && rstd && gamma && beta && y16, "vt_batchnorm_apply_x16: null argument");
+    if (bn_apply_x16_launch(x, B, L, C, mean, rstd, gamma, beta, act, up, y16, S(stream))) return VT_ERR_ARG;
+    VT_LAUNCH_CHECK("vt_batchnorm_apply_x16");
     return VT_OK;
 }
 

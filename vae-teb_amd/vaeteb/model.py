@@ -320,14 +320,18 @@ class ConvBlock(nn.Module):
         self.sync_bn = False      # cross-rank BatchNorm statistics (convert_sync_batchnorm)
         self.sync_group = None    # process group of the synchronised statistics (None: the default group)
 
-    def forward(self, x, xin=None, vout=False):
+    def forward(self, x, xin=None, vout=False, x16=None, y16=None):
         """xin / vout: ConvStack's BatchNorm fold (ops.ConvBNActF) — x is the previous block's
-        pre-BN output with its BatchNorm xin, and vout returns (pre-BN output, its BatchNorm)."""
+        pre-BN output with its BatchNorm xin, and vout returns (pre-BN output, its BatchNorm).
+        x16 / y16: ConvStack's staged 16-bit hand-off — x16 the previous block's output as this
+        block's operand rows (x its gradient handle), y16 the next block's `up` flag: returns
+        (handle, rows) for that block."""
         bn = self.bn_layer
-        if xin is not None or vout:
+        if xin is not None or vout or x16 is not None or y16 is not None:
             out = ops.conv_bn_act(x, self.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                   mode=0 if self.causal else 1, up=self.up, act="tanh" if self.tanh else "relu",
-                                  momentum=bn.momentum, eps=bn.eps, bf16=self.bf16, xin=xin, vout=vout)
+                                  momentum=bn.momentum, eps=bn.eps, bf16=self.bf16, xin=xin, vout=vout,
+                                  x16=x16, y16=y16)
             if not getattr(bn, "_vt_batched", False):
                 bn.num_batches_tracked.add_(1)
             return out
@@ -355,15 +359,39 @@ CONV_FOLD = int(os.environ.get("VAETEB_CONV_FOLD", "0"))
 
 
 class ConvStack(nn.Sequential):
-    """nn.Sequential of ConvBlocks (same children / state_dict keys).  Training with the bf16
-    conv kernels: each inner block hands the next its pre-BN output and BatchNorm instead of
+    """nn.Sequential of ConvBlocks (same children / state_dict keys).  Training with the 16-bit
+    conv kernels (no cross-rank BatchNorm): each inner block writes its output once as the next
+    block's staged 16-bit operand rows (ops.ConvBNActF x16 / y16: the x2 upsample applied,
+    channel stride ceil8(C)) in place of the fp32 y, and the next block copies those rows into
+    its forward and weight-gradient windows — the same operand bits, so the same values as
+    block by block; eval, fp32 and sync_bn stacks run block by block.
+
+    CONV_FOLD = 1 (bf16, measured slower): each inner block hands the next its pre-BN output and BatchNorm instead of
     y = act(BN(conv)) — the next block applies them while staging its windows, forward and
     weight gradient (ops.ConvBNActF) — so the inner outputs never round-trip through HBM and
     the separate BatchNorm-apply pass of every inner block is gone.  Same values as the
     unfolded stack (the staged operand is the y the apply pass would have written)."""
 
+    def _staged(self, blocks, x):
+        """The staged 16-bit hand-off applies: training with the 16-bit conv kernels, no
+        cross-rank statistics, every inner output needing its gradient (as the fold), and the
+        consumers within the flat kernels' shapes (K <= 11, <= 128 channels)."""
+        return (len(blocks) > 1 and x.is_cuda and
+                all(isinstance(b, ConvBlock) and b.training and b.bf16 and not b.sync_bn for b in blocks) and
+                len({b.bf16 for b in blocks}) == 1 and
+                torch.is_grad_enabled() and all(b.conv.weight.requires_grad for b in blocks[:-1]) and
+                all(b.conv.kernel_size <= 11 and b.conv.in_channels <= 128 and b.conv.out_channels <= 128
+                    for b in blocks[1:]))
+
     def forward(self, x):
         blocks = list(self)
+        if not CONV_FOLD and self._staged(blocks, x):
+            # each inner block writes its output once as the next block's 16-bit operand rows (x2
+            # upsample applied) in place of the fp32 y; the handle h only carries dL/dy back
+            h, rows = blocks[0](x, y16=blocks[1].up)
+            for i in range(1, len(blocks) - 1):
+                h, rows = blocks[i](h, x16=rows, y16=blocks[i + 1].up)
+            return blocks[-1](h, x16=rows)
         if not (CONV_FOLD and len(blocks) > 1 and x.is_cuda and
                 all(isinstance(b, ConvBlock) and b.training and b.bf16 == "bf16" and not b.sync_bn for b in blocks) and
                 not any(b.tanh for b in blocks[:-1]) and   # the staging applies the inner blocks' ReLU

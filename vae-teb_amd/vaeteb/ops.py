@@ -685,30 +685,52 @@ class ConvBNActF(torch.autograd.Function):
     vt_conv1d_bn_fwd_bf16_in / vt_conv1d_bwd_weight_bf16_in); vout returns this block's pre-BN
     output in place of y (with its mean / rstd, non-differentiable) for the next block to stage
     the same way — the inner blocks' y is never written or read.  The gradient autograd passes
-    back for that output is dL/dy (the next block's backward-data conv output), as for y."""
+    back for that output is dL/dy (the next block's backward-data conv output), as for y.
+
+    Staged hand-off (16-bit kernels; ConvStack's default): y16 = the NEXT block's `up` flag makes
+    this block write y once as that block's 16-bit operand rows (vt_conv1d_bn_fwd_bf16_x16: the
+    x2 upsample applied, channel stride ceil8(Cout), padding 0) instead of the fp32 y, and return
+    (handle, rows): handle is a (B, L_out, Cout) fp32 view without storage of its own, which only
+    carries dL/dy back through autograd.  x16 = such rows makes them this block's input (x is
+    then the handle), read as 16-byte segments by the forward and saved for the weight gradient
+    (vt_conv1d_bwd_weight_bf16_x16) in place of the fp32 input."""
 
     @staticmethod
-    def forward(ctx, x, w, g, b, run_mean, run_var, mode, up, act, momentum, eps, bf16=False, xin=None, vout=False):
+    def forward(ctx, x, w, g, b, run_mean, run_var, mode, up, act, momentum, eps, bf16=False, xin=None, vout=False,
+                x16=None, y16=None):
         _check(x, w, g, b)
         if (xin is not None or vout) and bf16 != "bf16":
             raise ValueError("the conv-stack BatchNorm fold needs the bf16 conv kernels (no fp32 / fp16 form)")
+        if (x16 is not None or y16 is not None) and (not bf16 or xin is not None or vout):
+            raise ValueError("the staged 16-bit hand-off needs the 16-bit conv kernels (and excludes the fold)")
         _h16(bf16)
         B, L, Cin = x.shape
         Cout, _, K = w.shape
-        x = x.contiguous()
+        if x16 is None:
+            x = x.contiguous()
         Lo = _lib.lib().fns["vt_conv1d_out_len"](L, K, mode, up)
         conv = torch.empty((B, Lo, Cout), device=x.device)
-        y = None if vout else torch.empty_like(conv)
+        y = None if vout or y16 is not None else torch.empty_like(conv)
         mean = torch.empty(Cout, device=x.device)
         rstd = torch.empty(Cout, device=x.device)
         ws = WS.get(_conv_bn_ws(B, L, Cin, Cout, K, mode, up), x.device, 2)
         w16t = None
+        rows = None
         if bf16:
             w16, w16t = _conv_shadow(w)
             tail = (B, L, Cin, ptr(w16), Cout, K, mode, up, ptr(g), ptr(b), ACT[act], eps, momentum, ptr(conv),
-                    None if vout else ptr(y), ptr(mean), ptr(rstd), ptr(run_mean), ptr(run_var), ptr(ws), ws.numel(),
-                    _st())
-            if xin is not None:
+                    None if y is None else ptr(y), ptr(mean), ptr(rstd), ptr(run_mean), ptr(run_var), ptr(ws),
+                    ws.numel(), _st())
+            if x16 is not None or y16 is not None:
+                if y16 is not None:
+                    rows = torch.empty((B, Lo * (2 if y16 else 1), (Cout + 7) // 8 * 8), dtype=_shadow_dtype(),
+                                       device=x.device)
+                if x16 is not None and (x16.dtype != _shadow_dtype() or not x16.is_contiguous() or
+                                        x16.shape != (B, L * (2 if up else 1), (Cin + 7) // 8 * 8)):
+                    raise ValueError(f"staged input rows: {x16.dtype} {tuple(x16.shape)}")
+                call("vt_conv1d_bn_fwd_bf16_x16", None if x16 is not None else ptr(x), ptr(x16), *tail[:-1],
+                     ptr(rows), int(bool(y16)), _st())
+            elif xin is not None:
                 call("vt_conv1d_bn_fwd_bf16_in", ptr(x), *(ptr(t) for t in xin[:4]), xin[4], *tail)
             else:
                 call("vt_conv1d_bn_fwd_bf16", ptr(x), *tail)
@@ -716,14 +738,21 @@ class ConvBNActF(torch.autograd.Function):
             call("vt_conv1d_bn_fwd", ptr(x), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(g), ptr(b), ACT[act], eps,
                  momentum, ptr(conv), ptr(y), ptr(mean), ptr(rstd), ptr(run_mean), ptr(run_var), ptr(ws), ws.numel(),
                  _st())
-        ctx.save_for_backward(x, conv, mean, rstd, w16t, *(xin[:4] if xin is not None else ()))
+        # a staged input is saved in place of x (the handle has no storage worth keeping)
+        ctx.save_for_backward(x16 if x16 is not None else x, conv, mean, rstd, w16t,
+                              *(xin[:4] if xin is not None else ()))
         ctx.params = (w, g, b)
         ctx.cfg = (mode, up, act, bf16)
         ctx.in_act = None if xin is None else xin[4]
+        ctx.x16 = (B, L, Cin) if x16 is not None else None
         if vout:
             ctx.mark_non_differentiable(mean, rstd)
             ctx.set_materialize_grads(False)   # no zero-filled gradients for mean / rstd
             return conv, mean, rstd
+        if y16 is not None:
+            ctx.mark_non_differentiable(rows)
+            ctx.set_materialize_grads(False)
+            return torch.empty(1, device=x.device).expand(B, Lo, Cout), rows
         return y
 
     @staticmethod
@@ -737,7 +766,8 @@ class ConvBNActF(torch.autograd.Function):
         # the input is the previous block's pre-BN output: its BatchNorm + act in the weight
         # gradient's staging (the backward-data output below is dL/d(that block's y), as always)
         inb = (*(ptr(t) for t in xin), ctx.in_act) if xin else None
-        B, L, Cin = x.shape
+        x16 = ctx.x16 is not None   # x holds the staged 16-bit input rows
+        B, L, Cin = ctx.x16 if x16 else x.shape
         Cout, _, K = w.shape
         Lo = conv.shape[1]
         gy = gy.contiguous()
@@ -767,6 +797,7 @@ class ConvBNActF(torch.autograd.Function):
                 dw_args = lambda wsx: (None, ptr(dxbn), c32, ptr(x), *inb, B, L, Cin, Cout, K, mode, up,
                                        ptr(pw.out[0]), pw.acc, ptr(wsx), wsx.numel(), _st())
                 fn = "vt_conv1d_bwd_weight_bf16_in"
+            dys = c32
         elif fused:
             # fused BatchNorm backward: only the column sums here; the bf16 backward-data
             # conv forms the BN input gradient while staging its operand from (gy, conv,
@@ -783,7 +814,10 @@ class ConvBNActF(torch.autograd.Function):
                 dw_args = lambda wsx: (None, ptr(dxbn), (Cout + 7) // 8 * 8, ptr(x), *inb, B, L, Cin, Cout, K, mode,
                                        up, ptr(pw.out[0]), pw.acc, ptr(wsx), wsx.numel(), _st())
                 fn = "vt_conv1d_bwd_weight_bf16_in"
+            dys = (Cout + 7) // 8 * 8
         else:
+            if x16:   # a staged input is the previous block's output: it always needs its gradient
+                raise RuntimeError("staged 16-bit hand-off: the block input's gradient is required")
             gconv = torch.empty_like(conv)
             call("vt_batchnorm_bwd", ptr(gy), ptr(conv), M, Cout, ptr(mean), ptr(rstd), ptr(g), ptr(b), ACT[act],
                  ptr(gconv), ptr(pbn.out[0]), ptr(pbn.out[1]), pbn.acc, ptr(ws), ws.numel(), _st())
@@ -793,9 +827,13 @@ class ConvBNActF(torch.autograd.Function):
             fn = "vt_conv1d_bwd_weight_bf16" if bf16 else "vt_conv1d_direct_bwd_weight"
             if inb:   # a folded input is the previous block's output: it always needs its gradient
                 raise RuntimeError("conv-stack fold: the block input's gradient is required")
+        if x16:   # the weight gradient's input operand: the staged rows, as 16-byte segments
+            dw_args = lambda wsx: (ptr(dxbn), dys, ptr(x), B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc,
+                                   ptr(wsx), wsx.numel(), _st())
+            fn = "vt_conv1d_bwd_weight_bf16_x16"
         gx = None
         if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
+            gx = torch.empty((B, L, Cin), device=conv.device)
             if bwd16:
                 edge = WS.get(max(B * 2 * pad * Cin, 1), x.device, 3)
                 call("vt_conv1d_bwd_dx16", ptr(dxbn), B, L, Cin, ptr(w16t), Cout, K, mode, up, ptr(gx), ptr(edge),
@@ -832,7 +870,7 @@ class ConvBNActF(torch.autograd.Function):
                 call(fn, *dw_args(ws1))
         gw, = pw.result()
         gg, gb = pbn.result()
-        return gx, gw, gg, gb, None, None, None, None, None, None, None, None, None, None
+        return gx, gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class SyncConvBNActF(torch.autograd.Function):
@@ -1391,11 +1429,12 @@ def layer_norm_act(x, g, b, act="none", eps=1e-5):
 
 
 def conv_bn_act(x, w, g, b, run_mean, run_var, mode, up=False, act="relu", momentum=0.9, eps=1e-5, bf16=False,
-                xin=None, vout=False):
+                xin=None, vout=False, x16=None, y16=None):
     """xin / vout: the conv-stack BatchNorm fold (ConvBNActF); vout returns (pre-BN output, its
-    BatchNorm as the next block's xin)."""
+    BatchNorm as the next block's xin).  x16 / y16: the staged 16-bit hand-off (ConvBNActF); y16
+    (the next block's `up`) returns (handle, staged rows) for the next block's (x, x16)."""
     out = ConvBNActF.apply(x, w, g, b, run_mean, run_var, int(mode), int(up), act, momentum, eps, h16_flag(bf16), xin,
-                           bool(vout))
+                           bool(vout), x16, None if y16 is None else int(bool(y16)))
     if not vout:
         return out
     conv, mean, rstd = out
