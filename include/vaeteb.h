@@ -713,6 +713,10 @@ int vt_layernorm_bwd(const float* dy, const float* xhat, const float* rstd, int6
                      float* ws, int64_t ws_floats, void* stream);
 /* Train-mode BatchNorm1d (batch stats over M = B*L rows, momentum semantics of
  * torch, running stats updated in place) + activation.
+ * Alignment: the fp32 BatchNorm kernels move the activations as 16-byte vectors, so x, y, dy
+ * and dx of vt_batchnorm_fwd / _bwd / _fwd_dropout / _bwd_dropout / _bwd_coef,
+ * vt_batchnorm_apply, vt_syncbn_sums and vt_syncbn_bwd_dx must be 16-byte aligned
+ * (VT_ERR_ARG before any launch otherwise; a NULL dy of vt_syncbn_sums passes).
  * replaces: nn.BatchNorm1d(C, momentum=0.9) + ReLU/tanh (vae_teb_model.py:175, :230) */
 int vt_batchnorm_fwd(const float* x, int64_t M, int C, const float* gamma, const float* beta, int act, float eps,
                      float momentum, float* y, float* mean, float* rstd, float* run_mean, float* run_var, float* ws,

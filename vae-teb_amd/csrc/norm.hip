@@ -1215,6 +1215,13 @@ int bn_apply_x16_launch(const float* x, int B, int L, int C, const float* mean, 
     return VT_OK;
 }
 
+// k_col_partial4, k_bn_apply4(d) and k_bn_dx4 read and write float4 at p + 4 k: the activation
+// pointers of the fp32 BatchNorm entry points are 16-byte aligned (NULL passes)
+template <typename... P>
+static inline bool aligned16(P... p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
 }  // namespace vt
 
 using namespace vt;
@@ -1330,6 +1337,7 @@ int vt_batchnorm_fwd(const float* x, int64_t M, int C, const float* gamma, const
                      float momentum, float* y, float* mean, float* rstd, float* run_mean, float* run_var, float* ws,
                      int64_t ws_floats, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256, "vt_batchnorm_fwd: shape (C <= 256)");
+    VT_CHECK_ARG(aligned16(x, y), "vt_batchnorm_fwd: x / y not 16-byte aligned");
     int64_t rpb;
     const int blocks = bn_blocks(M, ws_floats, C, &rpb);
     VT_CHECK_ARG(blocks >= 1, "vt_batchnorm_fwd: workspace too small");
@@ -1356,6 +1364,7 @@ int vt_batchnorm_fwd_dropout(const float* x, int64_t M, int C, const float* gamm
                              int64_t ws_floats, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256 && L >= 0 && (L == 0 || M % L == 0) && p >= 0.f && p < 1.f,
                  "vt_batchnorm_fwd_dropout: shape (C <= 256, M a multiple of L) / 0 <= p < 1");
+    VT_CHECK_ARG(aligned16(x, y), "vt_batchnorm_fwd_dropout: x / y not 16-byte aligned");
     int64_t rpb;
     const int blocks = bn_blocks(M, ws_floats, C, &rpb);
     VT_CHECK_ARG(blocks >= 1, "vt_batchnorm_fwd_dropout: workspace too small");
@@ -1386,6 +1395,7 @@ int vt_batchnorm_bwd(const float* dy, const float* x, int64_t M, int C, const fl
                      const float* gamma, const float* beta, int act, float* dx, float* dgamma, float* dbeta,
                      int accumulate_params, float* ws, int64_t ws_floats, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256, "vt_batchnorm_bwd: shape");
+    VT_CHECK_ARG(aligned16(dy, x, dx), "vt_batchnorm_bwd: dy / x / dx not 16-byte aligned");
     int64_t rpb;
     const int blocks = bn_blocks(M, ws_floats - 2 * C, C, &rpb);
     VT_CHECK_ARG(blocks >= 1, "vt_batchnorm_bwd: workspace too small");
@@ -1411,6 +1421,7 @@ int vt_batchnorm_bwd_dropout(const float* dy, const float* x, int64_t M, int C, 
                              float* ws, int64_t ws_floats, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256 && L >= 0 && (L == 0 || M % L == 0) && p >= 0.f && p < 1.f,
                  "vt_batchnorm_bwd_dropout: shape (C <= 256, M a multiple of L) / 0 <= p < 1");
+    VT_CHECK_ARG(aligned16(dy, x, dx), "vt_batchnorm_bwd_dropout: dy / x / dx not 16-byte aligned");
     if (p == 0.f)
         return vt_batchnorm_bwd(dy, x, M, C, mean, rstd, gamma, beta, act, dx, dgamma, dbeta, accumulate_params, ws,
                                 ws_floats, stream);
@@ -1441,6 +1452,7 @@ int vt_batchnorm_bwd_coef(const float* dy, const float* x, int64_t M, int C, con
                           const float* gamma, const float* beta, int act, float* dgamma, float* dbeta,
                           int accumulate_params, float* bnp, float* ws, int64_t ws_floats, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256 && bnp, "vt_batchnorm_bwd_coef: shape");
+    VT_CHECK_ARG(aligned16(dy, x), "vt_batchnorm_bwd_coef: dy / x not 16-byte aligned");
     int64_t rpb;
     const int blocks = bn_blocks(M, ws_floats, C, &rpb);
     VT_CHECK_ARG(blocks >= 1, "vt_batchnorm_bwd_coef: workspace too small");
@@ -1478,6 +1490,7 @@ int vt_syncbn_sums(const float* x, const float* dy, int64_t M, int C, int which,
     VT_CHECK_ARG(M > 0 && C > 0 && C <= 256 && which >= 0 && which <= 2 && sums, "vt_syncbn_sums: shape");
     VT_CHECK_ARG(which == 0 || mean, "vt_syncbn_sums: mean needed");
     VT_CHECK_ARG(which < 2 || (dy && rstd && gamma && beta), "vt_syncbn_sums: backward arguments");
+    VT_CHECK_ARG(aligned16(x, dy), "vt_syncbn_sums: x / dy not 16-byte aligned");
     int64_t rpb;
     const int blocks = bn_blocks(M, ws_floats, C, &rpb);
     VT_CHECK_ARG(blocks >= 1, "vt_syncbn_sums: workspace too small");
@@ -1502,6 +1515,7 @@ int vt_syncbn_stats(const double* sums, int C, int which, float eps, float momen
 int vt_batchnorm_apply(const float* x, int64_t M, int C, const float* mean, const float* rstd, const float* gamma,
                        const float* beta, int act, float* y, void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= BNV_C, "vt_batchnorm_apply: shape");
+    VT_CHECK_ARG(aligned16(x, y), "vt_batchnorm_apply: x / y not 16-byte aligned");
     bn_apply_vec(x, M, C, mean, rstd, gamma, beta, act, y, S(stream));
     VT_LAUNCH_CHECK("vt_batchnorm_apply");
     return VT_OK;
@@ -1519,6 +1533,7 @@ int vt_syncbn_bwd_dx(const float* dy, const float* x, int64_t M, int C, const fl
                      const float* gamma, const float* beta, int act, const double* sums, float* dx, float* ws,
                      void* stream) {
     VT_CHECK_ARG(M > 0 && C > 0 && C <= BNV_C && sums && ws, "vt_syncbn_bwd_dx: arguments");
+    VT_CHECK_ARG(aligned16(dy, x, dx), "vt_syncbn_bwd_dx: dy / x / dx not 16-byte aligned");
     hipStream_t st = S(stream);
     float* dg = ws;
     float* db = ws + C;
