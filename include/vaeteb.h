@@ -349,6 +349,49 @@ int vt_te_latent_rows(const float* mu_c, const float* lv_q, const float* mu_y, c
  * replaces: the per-sample numpy metrics ref/model/graph_model.py:1606-1645 and :1842-1851      */
 int vt_recon_metrics_rows(const float* y, const float* pr, int64_t B, int K, int64_t n, float* out, void* stream);
 
+/* ------------------------------------------------- windows -> recording timelines
+ * Overlapping windows stitched into packed per-recording timelines (vaeteb/timeline.py): position p of
+ * a packed timeline of `total` positions carries the running sums acc[p] (float32: sum of w*v),
+ * wacc[p] (float32: sum of w) and count[p] (int32: windows seen), zeroed by the caller before the first
+ * call.  Gather form: every position is owned by one thread (inner == 1) or one half-wave (inner > 1),
+ * which finds its covering windows in the ascending offset table (binary search for p - n + 1, then a
+ * forward scan) and adds them in ascending window order.  No atomics, no dependence on the launch
+ * geometry; equal inputs give equal bits, and an ascending window list split into consecutive calls
+ * gives the bits of the single call (the sums continue in the buffers, every position in the same
+ * order).  All three return VT_ERR_ARG before any device work for a bad size or a null pointer.
+ *
+ * acc/wacc/count += contributions of W windows.  vals (W, n, inner) float32; window w covers packed
+ * positions [dst_off[w], dst_off[w] + len[w]) (len NULL: all n; else 0 <= len[w] <= n).  dst_off
+ * (device int64[W]) ascending, duplicates allowed; the caller guarantees 0 <= dst_off[w] and
+ * dst_off[w] + len[w] <= total (checked on the host copy by the Python wrapper; the kernel touches
+ * no position outside [0, total) whatever the table holds).  The value of window w at position p is
+ * v = float(sum_l (double)vals[w, p - dst_off[w], l] / inner) (one rounding); its weight
+ * blend 0 (mean): 1; blend 1 (taper): min(i + 1, n - i), i = p - dst_off[w] (over the full n, not
+ * shortened by len).  acc += w*v (float32 product, then float32 sum), wacc += w, count += 1.  A
+ * position no window of the call covers is not written.  W == 0: no-op.
+ * replaces: the (B, N, new_C) NaN canvas loop of SeqVaeTeb.get_predictions
+ *           (ref/model/vae_teb_model.py:1228-1244); the stitching of a recording's windows has
+ *           no reference counterpart (the reference scores windows only)                        */
+int vt_timeline_accumulate(const float* vals, int64_t W, int n, int inner, const int64_t* dst_off, const int* len,
+                           int blend, float* acc, float* wacc, int* count, int64_t total, void* stream);
+/* out[p] = count[p] ? (acc[p] / wacc[p]) * scale + shift : fill, p < total: the float32 quotient, then
+ * the float32 product, then the float32 sum, each rounded (never contracted into an fma).  scale 1,
+ * shift 0: the plain (weighted) mean; scale = std + 1e-8f, shift = mean: denormalize_signal_data.
+ * replaces: torch.nanmean(y, dim=1) ref/model/vae_teb_model.py:1246 and denormalize_signal_data
+ *           ref/model/graph_model.py:83-85                                                      */
+int vt_timeline_finish(const float* acc, const float* wacc, const int* count, int64_t total, float fill,
+                       float scale, float shift, float* out, void* stream);
+/* per recording r over positions [base[r], base[r+1]) with count > 0: (R, 5) = vaf, mse, snr_db,
+ * vaf_unclamped, covered fraction.  y, recon, count: packed (base[R]) arrays; base: device int64[R+1]
+ * ascending.  The first four are vt_recon_metrics_rows's definitions and arithmetic (float32 residual
+ * y - recon, every term widened to double, means then centred squares, population variances, the
+ * 1e-12 thresholds, fixed-order wave and LDS sums) over the covered positions only; NaN when none
+ * is covered.  Covered fraction = covered / (base[r+1] - base[r]) (0 for an empty recording).  One
+ * workgroup per recording.  R == 0: no-op.
+ * replaces: the per-sample numpy metrics ref/model/graph_model.py:1619-1645, per recording     */
+int vt_timeline_metrics(const float* y, const float* recon, const int* count, const int64_t* base, int64_t R,
+                        float* out, void* stream);
+
 /* ----------------------------------------------------------------- optimiser
  * Flat fp32 buffers: every parameter / gradient / moment is a view of one
  * contiguous allocation.                                                        */

@@ -887,6 +887,17 @@ class SeqVaeTeb(nn.Module):
         1510-1680): up_gain_sweep with the single gain 1, every result (B, 1)."""
         return self.up_gain_sweep(y_st, y_ph, x_ph, y_raw, gains=(1.0,), **kw)
 
+    def score_recordings(self, frontend, windows, **kw):
+        """Whole recordings: the kept windows of `windows` (a vaeteb.windows.RecordingWindows) scored
+        and stitched into per-recording transfer-entropy and reconstruction timelines with
+        per-recording metrics: vaeteb.timeline.RecordingScorer(self, frontend)(windows, **kw), the
+        scorer kept for the next call with the same front-end.  Returns a RecordingTimelines."""
+        from .timeline import RecordingScorer
+        scorer = self.__dict__.get("_recording_scorer")
+        if scorer is None or scorer.frontend is not frontend:
+            scorer = self.__dict__["_recording_scorer"] = RecordingScorer(self, frontend)
+        return scorer(windows, **kw)
+
     @staticmethod
     def get_predictions(x, stride=16, new_C=4800):
         """ref/model/vae_teb_model.py:1228-1246: overlapping per-step windows x (B, N, C)
