@@ -332,3 +332,43 @@ def test_lstm16_quad_chained_bitwise_pairs(ops, monkeypatch, In, B, S):
     for run in (1, 2):
         for k, (a, b) in enumerate(zip(outs[0], outs[run])):
             assert torch.equal(a, b), (run, k, (a != b).sum().item(), (a - b).abs().max().item())
+
+
+@pytest.mark.parametrize("In", [72, 80])
+def test_lstm16_mixed_plan_bitwise_split(ops, monkeypatch, In):
+    """A plan whose groups do not start at layer 0: In > 64 puts layer 0 on the fp32 unfused path
+    (In = 72: the one-pass vt_lstm_layer_bwd_weight; In = 80: In + 64 + 1 > 144, two
+    vt_linear_bwd_weight + two vt_colsum) and layers 1-3 on a pair plus one single 16-bit layer.
+    The four-layer op == the same layers split through autograd (layer 0 as one op, layers 1-3 as
+    another) bit for bit: output, dx and all 16 parameter gradients; S = 17 is not a multiple of
+    the 16-step chunk."""
+    B, S, nl = 3, 17, 4
+    torch.manual_seed(23)
+    ref = torch.nn.LSTM(In, 64, nl, batch_first=True)
+    params = [p.detach().cuda() for p in ref.parameters()]
+    x = torch.randn(B, S, In, device="cuda")
+    gy = torch.randn(B, S, 64, device="cuda")
+    outs, names = [], []
+    real_call = ops.call
+    for split in (False, True):
+        called = []
+        monkeypatch.setattr(ops, "call", lambda name, *a: (called.append(name), real_call(name, *a))[1])
+        pd = [p.clone().requires_grad_() for p in params]
+        xd = x.clone().requires_grad_()
+        if split:
+            y = ops.lstm(ops.lstm(xd, pd[:4], half=True), pd[4:], half=True)
+        else:
+            y = ops.lstm(xd, pd, half=True)
+        y.backward(gy)
+        torch.cuda.synchronize()
+        outs.append([y.detach(), xd.grad] + [p.grad for p in pd])
+        names.append(called)
+    for fn in ("vt_lstm_layer_fwd", "vt_lstm16_pair_fwd", "vt_lstm16_layer_fwd", "vt_lstm16_pair_bwd",
+               "vt_lstm16_layer_bwd"):
+        assert names[0].count(fn) == 1, (fn, names[0])
+    assert not [n for n in names[0] if n.startswith("vt_lstm16_quad_")], names[0]
+    bw = [n for n in names[0] if n in ("vt_lstm_layer_bwd_weight", "vt_linear_bwd_weight", "vt_colsum")]
+    assert bw == (["vt_lstm_layer_bwd_weight"] if In == 72 else ["vt_linear_bwd_weight"] * 2 + ["vt_colsum"] * 2), bw
+    assert len(outs[0]) == 18
+    for k, (a, b) in enumerate(zip(*outs)):
+        assert torch.equal(a, b), (k, (a != b).sum().item(), (a - b).abs().max().item())

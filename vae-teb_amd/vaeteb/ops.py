@@ -7,6 +7,7 @@ so no transposes are needed between the MLP, conv and LSTM stages (the
 reference transposes to (B, C, L) for torch's conv1d at
 ref/model/vae_teb_model.py:539,545,693,917).
 """
+import collections
 import ctypes
 import os
 
@@ -155,6 +156,24 @@ CONV_DIRECT_DX = int(os.environ.get("VAETEB_CONV_DIRECT_DX", "1"))
 # conv-block backward as vt_batchnorm_bwd_x16 + vt_conv1d_bwd_dx16 (bf16 operand written once,
 # upsample fold inside the conv); 0: the fused-staging kernels (vt_conv1d_bwd_*_bf16_bn)
 CONV_BWD16 = int(os.environ.get("VAETEB_CONV_BWD16", "1"))
+
+
+def _on_grad_stream(side, reads, launch):
+    """Run launch() on the weight-gradient stream `side` (GRAD_STREAM, HEAD_GRAD_STREAM or
+    LSTM_GRAD_STREAM as the caller read it; None: none applies): `side` waits for the work enqueued
+    so far on the current stream, and `reads`, the tensors launch() reads, are kept from reuse
+    until it has run.  Without a side stream (or already on it) launch() runs in line.  launch()
+    fetches its own workspace: WS and the caching allocator both hand out buffers per stream.
+    Returns whether the work went to `side`."""
+    if side is None or side.cuda_stream == _lib.stream():
+        launch()
+        return False
+    _lib.wait_for(side)
+    with torch.cuda.stream(side):
+        launch()
+    for t in reads:
+        t.record_stream(side)
+    return True
 
 
 class _ParamGrads:
@@ -322,8 +341,13 @@ class LinearF(torch.autograd.Function):
             else:
                 FIRST_WRITER[id(w)] = ent   # not written here: handled after the backward
         if gw_t is not None:
-            pre = "vt_mfma_" if ctx.mfma else "vt_"
-            side = HEAD_GRAD_STREAM if (ctx.mfma and pg.direct and HEAD_GRAD_STREAM is not None) else None
+            fn = "vt_mfma_linear_bwd_weight" if ctx.mfma else "vt_linear_bwd_weight"
+
+            def dw():
+                ws_w = WS.get(WS_LINEAR, w.device, 1)
+                call(fn, ptr(gy2), R, N, ptr(x2), K, ptr(gw_t), ptr(gb_t), pg.acc, ptr(ws_w), ws_w.numel(), _st())
+
+            side = HEAD_GRAD_STREAM if (ctx.mfma and pg.direct) else None
             if side is None and ctx.mfma and pg.direct and HEAD_DW_DEFER and GRAD_READY is None:
                 # no side stream for them (under capture the branch is dropped, model.py): the
                 # heads' weight gradients are enqueued at the end of this backward instead of
@@ -332,34 +356,22 @@ class LinearF(torch.autograd.Function):
                 # only: with bucketed all-reduce hooks the heads' bucket must be ready early)
                 cs = torch.cuda.current_stream()
 
-                def run(gy2=gy2, x2=x2, pg=pg, cs=cs, R=R, N=N, K=K, pre=pre, fmt=ctx.mfma):
+                def run(fmt=ctx.mfma):
                     _h16(fmt)
                     with torch.cuda.stream(cs):
-                        ws_d = WS.get(WS_LINEAR, gy2.device, 1)
-                        call(pre + "linear_bwd_weight", ptr(gy2), R, N, ptr(x2), K, ptr(pg.out[0]), ptr(pg.out[1]),
-                             pg.acc, ptr(ws_d), ws_d.numel(), _st())
+                        dw()
                     pg.result()
                 _defer(run)
                 return gx, None, None, None
-            if side is not None and side.cuda_stream != _lib.stream():
-                # the decoder heads' 4096 x 4096 weight gradients are off the data-gradient
-                # chain: a side stream idle during the decoder backward (in-place sinks)
-                _lib.wait_for(side)
-                with torch.cuda.stream(side):
-                    ws_s = WS.get(WS_LINEAR, w.device, 1)
-                    call(pre + "linear_bwd_weight", ptr(gy2), R, N, ptr(x2), K, ptr(gw_t), ptr(gb_t), pg.acc,
-                         ptr(ws_s), ws_s.numel(), _st())
-                gy2.record_stream(side)
-                x2.record_stream(side)
+            # the decoder heads' 4096 x 4096 weight gradients are off the data-gradient
+            # chain: a side stream idle during the decoder backward (in-place sinks)
+            if _on_grad_stream(side, (gy2, x2), dw):
                 if CAPTURE_TRACE and torch.cuda.is_current_stream_capturing():   # diagnostic (capture_probe.py)
                     import sys
                     print(f"[capture] head branch enqueued on side stream:\n{_lib.capture_info(side)}\n"
                           f"[capture] the decoder's stream:\n{_lib.capture_info()}", file=sys.stderr, flush=True)
                 if HEAD_GRAD_JOIN:   # diagnostic (tools/capture_probe.py model_head_join)
                     _lib.wait_for(_lib.stream(), side)
-            else:
-                call(pre + "linear_bwd_weight", ptr(gy2), R, N, ptr(x2), K, ptr(gw_t), ptr(gb_t), pg.acc, ptr(ws),
-                     ws.numel(), _st())
         elif gb_t is not None:
             call("vt_colsum", ptr(gy2), R, N, ptr(gb_t), pg.acc, ptr(ws), ws.numel(), _st())
         gw, gb = pg.result()
@@ -433,7 +445,6 @@ class MlpSpec:
     MAX_LAYERS, MAX_WIDTH = 34, 144   # VT_MLP_MAX_LAYERS / VT_MLP_MAX_WIDTH
 
     def __init__(self, dims, layer_ln, layer_act, skip, eps):
-        import ctypes
         self.L = len(dims) - 1
         self.dims_l, self.skip, self.eps = list(dims), int(skip), float(eps)
         self.dims = (ctypes.c_int * len(dims))(*dims)
@@ -453,7 +464,6 @@ class MlpSpec:
         the split bf16 backward (vt_resmlp_bf16_bwd_data / _bwd_weight)."""
         s = self._sizes.get((rows, "split"))
         if s is None:
-            import ctypes
             arr = (ctypes.c_int64 * 4)()
             call("vt_resmlp_bf16_split_sizes", self.L, self.dims, self.ln, self.act, self.skip, rows, arr)
             s = self._sizes[(rows, "split")] = tuple(arr)
@@ -462,7 +472,6 @@ class MlpSpec:
     def sizes(self, rows, bf16=False):
         s = self._sizes.get((rows, bf16))
         if s is None:
-            import ctypes
             arr = (ctypes.c_int64 * 3)()
             call("vt_resmlp_bf16_sizes" if bf16 else "vt_resmlp_sizes", self.L, self.dims, self.ln, self.act,
                  self.skip, rows, arr)
@@ -471,7 +480,6 @@ class MlpSpec:
 
     @staticmethod
     def pointers(ts):
-        import ctypes
         return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
     def plan_handle(self, rows, params):
@@ -481,7 +489,6 @@ class MlpSpec:
         key = (rows, tuple(pp))
         h = getattr(self, "_handles", {}).get(key)
         if h is None:
-            import ctypes
             hv = ctypes.c_int64()
             call("vt_resmlp_bf16_plan", self.L, self.dims, self.ln, self.act, self.skip, self.eps, pp, rows,
                  ctypes.byref(hv), _st())
@@ -493,7 +500,6 @@ class MlpSpec:
         (the trainer's in-place gradient sinks)."""
         key = tuple(0 if t is None else t.data_ptr() for t in ts)
         if key != self._grad_key:
-            import ctypes
             self._grad_key = key
             self._grad_ptrs = (ctypes.c_void_p * len(ts))(*[k or None for k in key])
         return self._grad_ptrs
@@ -511,7 +517,6 @@ def mlp_prep_batch(stacks, rows):
     16-bit ResidualMLP forwards (14 launches of ~7 us each on the forward chain) become one."""
     if not stacks:
         return
-    import ctypes
     hs = [spec.plan_handle(rows, params) for spec, params in stacks]
     for i in range(0, len(hs), 32):
         chunk = hs[i:i + 32]
@@ -578,19 +583,13 @@ class ResMLPF(torch.autograd.Function):
             gp = spec.grad_pointers(grads)
             call("vt_resmlp_bf16_bwd_data", spec.L, spec.dims, spec.ln, spec.act, spec.skip, spec.eps, pp, ptr(g2),
                  ptr(xh), ptr(rs), R, ptr(dx), gp, pg.acc, ptr(dz16), ptr(wsx), wsx.numel(), _st())
-            side = GRAD_STREAM if (pg.direct and GRAD_STREAM is not None) else None
-            if side is not None and side.cuda_stream != _lib.stream():
-                _lib.wait_for(side)
-                with torch.cuda.stream(side):
-                    wsw = torch.empty(n_ww, device=xh.device)
-                    call("vt_resmlp_bf16_bwd_weight", spec.L, spec.dims, spec.ln, spec.act, spec.skip, spec.eps, pp,
-                         ptr(xh), ptr(dz16), R, gp, pg.acc, ptr(wsw), wsw.numel(), _st())
-                dz16.record_stream(side)
-                xh.record_stream(side)
-            else:
+
+            def dw():
                 wsw = torch.empty(n_ww, device=xh.device)
                 call("vt_resmlp_bf16_bwd_weight", spec.L, spec.dims, spec.ln, spec.act, spec.skip, spec.eps, pp,
                      ptr(xh), ptr(dz16), R, gp, pg.acc, ptr(wsw), wsw.numel(), _st())
+
+            _on_grad_stream(GRAD_STREAM if pg.direct else None, (dz16, xh), dw)
         else:
             ws_floats = spec.sizes(R, bool(bf16))[2]
             ws = WS.get(ws_floats, xh.device, 5)
@@ -668,11 +667,28 @@ def _conv_shadow(w, prepass=False):
 def _conv_bn_ws(*shape):
     n = _CONV_WS.get(shape)
     if n is None:
-        import ctypes
         f = ctypes.c_int64()
         call("vt_conv1d_bn_workspace_floats", *shape, ctypes.byref(f))
         n = _CONV_WS[shape] = max(int(f.value), 4096 * shape[3] + 2 * shape[3])
     return n
+
+
+def _conv_fwd(x, w, mode, up, bf16):
+    """The conv alone, (B, L, Cin) contiguous -> (B, L_out, Cout): on the 16-bit shadow of w
+    (bf16: False, "bf16" or "fp16") or the fp32 direct kernel.  Returns (conv, w16t), w16t the
+    transposed shadow for a backward-data conv (None in fp32)."""
+    B, L, Cin = x.shape
+    Cout, _, K = w.shape
+    Lo = _lib.lib().fns["vt_conv1d_out_len"](L, K, mode, up)
+    conv = torch.empty((B, Lo, Cout), device=x.device)
+    w16t = None
+    if bf16:
+        _h16(bf16)
+        w16, w16t = _conv_shadow(w)
+        call("vt_conv1d_fwd_bf16", ptr(x), B, L, Cin, ptr(w16), Cout, K, mode, up, ptr(conv), _st())
+    else:
+        call("vt_conv1d_direct_fwd", ptr(x), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(conv), _st())
+    return conv, w16t
 
 
 class ConvBNActF(torch.autograd.Function):
@@ -782,95 +798,80 @@ class ConvBNActF(torch.autograd.Function):
         # row image of Cout <= 1024 channels in LDS; other shapes keep the fused-staging kernels)
         bwd16 = fused and CONV_BWD16 and K <= 11 and B <= 65535 and Cout <= 1024 and \
             (mode == 1 and L * (2 if up else 1) > pad or mode == 0 and not up)
-        if bwd16:
+        # 1. BatchNorm backward -> dy, the conv's output gradient as the weight gradient reads it:
+        #    16-bit rows of row stride dys channels (bwd16: written here; fused: written by the
+        #    backward-data conv below), or fp32 (dys None)
+        if fused:
             bnp = torch.empty(6 * Cout, device=x.device)
             call("vt_batchnorm_bwd_coef", ptr(gy), ptr(conv), M, Cout, ptr(mean), ptr(rstd), ptr(g), ptr(b),
                  ACT[act], ptr(pbn.out[0]), ptr(pbn.out[1]), pbn.acc, ptr(bnp), ptr(ws), ws.numel(), _st())
-            c32 = (Cout + 31) // 32 * 32
-            dxbn = torch.empty(M * c32, dtype=_shadow_dtype(), device=x.device)
-            call("vt_batchnorm_bwd_x16", ptr(gy), ptr(conv), ptr(bnp), ACT[act], M, Cout, ptr(dxbn), _st())
-            srcs = (dxbn,)
-            dw_args = lambda wsx: (ptr(dxbn), c32, ptr(x), B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc,
-                                   ptr(wsx), wsx.numel(), _st())
-            fn = "vt_conv1d_bwd_weight_bf16_dy16s"
-            if inb:
-                dw_args = lambda wsx: (None, ptr(dxbn), c32, ptr(x), *inb, B, L, Cin, Cout, K, mode, up,
-                                       ptr(pw.out[0]), pw.acc, ptr(wsx), wsx.numel(), _st())
-                fn = "vt_conv1d_bwd_weight_bf16_in"
-            dys = c32
-        elif fused:
-            # fused BatchNorm backward: only the column sums here; the bf16 backward-data
-            # conv forms the BN input gradient while staging its operand from (gy, conv,
-            # bnp) and leaves it in bf16 (dxbn) for the weight gradient
-            bnp = torch.empty(6 * Cout, device=x.device)
-            call("vt_batchnorm_bwd_coef", ptr(gy), ptr(conv), M, Cout, ptr(mean), ptr(rstd), ptr(g), ptr(b),
-                 ACT[act], ptr(pbn.out[0]), ptr(pbn.out[1]), pbn.acc, ptr(bnp), ptr(ws), ws.numel(), _st())
-            dxbn = torch.empty(M * ((Cout + 7) // 8 * 8), dtype=torch.bfloat16, device=x.device)
-            srcs = (dxbn,)
-            dw_args = lambda wsx: (ptr(dxbn), ptr(x), B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc,
-                                   ptr(wsx), wsx.numel(), _st())
-            fn = "vt_conv1d_bwd_weight_bf16_dy16"
-            if inb:
-                dw_args = lambda wsx: (None, ptr(dxbn), (Cout + 7) // 8 * 8, ptr(x), *inb, B, L, Cin, Cout, K, mode,
-                                       up, ptr(pw.out[0]), pw.acc, ptr(wsx), wsx.numel(), _st())
-                fn = "vt_conv1d_bwd_weight_bf16_in"
-            dys = (Cout + 7) // 8 * 8
+            if bwd16:
+                dys = (Cout + 31) // 32 * 32
+                dy = torch.empty(M * dys, dtype=_shadow_dtype(), device=x.device)
+                call("vt_batchnorm_bwd_x16", ptr(gy), ptr(conv), ptr(bnp), ACT[act], M, Cout, ptr(dy), _st())
+            else:
+                # fused BatchNorm backward: only the column sums here; the bf16 backward-data
+                # conv forms the BN input gradient while staging its operand from (gy, conv,
+                # bnp) and leaves it in bf16 (dy) for the weight gradient
+                dys = (Cout + 7) // 8 * 8
+                dy = torch.empty(M * dys, dtype=torch.bfloat16, device=x.device)
         else:
             if x16:   # a staged input is the previous block's output: it always needs its gradient
                 raise RuntimeError("staged 16-bit hand-off: the block input's gradient is required")
-            gconv = torch.empty_like(conv)
+            dys = None
+            dy = torch.empty_like(conv)
             call("vt_batchnorm_bwd", ptr(gy), ptr(conv), M, Cout, ptr(mean), ptr(rstd), ptr(g), ptr(b), ACT[act],
-                 ptr(gconv), ptr(pbn.out[0]), ptr(pbn.out[1]), pbn.acc, ptr(ws), ws.numel(), _st())
-            srcs = (gconv,)
-            dw_args = lambda wsx: (ptr(gconv), ptr(x), B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc,
-                                   ptr(wsx), wsx.numel(), _st())
-            fn = "vt_conv1d_bwd_weight_bf16" if bf16 else "vt_conv1d_direct_bwd_weight"
+                 ptr(dy), ptr(pbn.out[0]), ptr(pbn.out[1]), pbn.acc, ptr(ws), ws.numel(), _st())
             if inb:   # a folded input is the previous block's output: it always needs its gradient
                 raise RuntimeError("conv-stack fold: the block input's gradient is required")
-        if x16:   # the weight gradient's input operand: the staged rows, as 16-byte segments
-            dw_args = lambda wsx: (ptr(dxbn), dys, ptr(x), B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc,
-                                   ptr(wsx), wsx.numel(), _st())
-            fn = "vt_conv1d_bwd_weight_bf16_x16"
+        # 2. dX
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty((B, L, Cin), device=conv.device)
             if bwd16:
                 edge = WS.get(max(B * 2 * pad * Cin, 1), x.device, 3)
-                call("vt_conv1d_bwd_dx16", ptr(dxbn), B, L, Cin, ptr(w16t), Cout, K, mode, up, ptr(gx), ptr(edge),
+                call("vt_conv1d_bwd_dx16", ptr(dy), B, L, Cin, ptr(w16t), Cout, K, mode, up, ptr(gx), ptr(edge),
                      _st())
             elif fused and CONV_DIRECT_DX and not up and (mode == 0 or L > pad):
                 # the fold is a crop: the conv writes gx itself (reflect: + the mirrored edge rows)
                 edge = WS.get(max(B * 2 * pad * Cin, 1), x.device, 3)
                 call("vt_conv1d_bwd_dx_bf16_bn", ptr(gy), ptr(conv), ptr(bnp), ACT[act], M, B, L, Cin, ptr(w16t),
-                     Cout, K, mode, up, ptr(gx), ptr(edge), ptr(dxbn), _st())
+                     Cout, K, mode, up, ptr(gx), ptr(edge), ptr(dy), _st())
             else:
                 gpad = WS.get(B * (Lo + K - 1) * Cin, x.device, 3)
                 if fused:
                     call("vt_conv1d_bwd_gpad_bf16_bn", ptr(gy), ptr(conv), ptr(bnp), ACT[act], M, B, L, Cin,
-                         ptr(w16t), Cout, K, mode, up, ptr(gpad), ptr(dxbn), _st())
+                         ptr(w16t), Cout, K, mode, up, ptr(gpad), ptr(dy), _st())
                 else:
-                    call("vt_conv1d_direct_bwd_gpad", ptr(gconv), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(gpad),
+                    call("vt_conv1d_direct_bwd_gpad", ptr(dy), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(gpad),
                          _st())
                 call("vt_conv1d_fold", ptr(gpad), B, L, Cin, Cout, K, mode, up, ptr(gx), 0, _st())
+        # 3. weight gradient: the entry point by (input kind, dy kind)
         pw = _ParamGrads([w], [ctx.needs_input_grad[1]])
         if pw.out[0] is not None:
-            side = GRAD_STREAM if (pw.direct and GRAD_STREAM is not None) else None
-            if side is not None and side.cuda_stream != _lib.stream():
-                # the weight gradient is off the data-gradient chain: compute it on a
-                # side stream (written in place into the flat gradient buffer, joined
-                # at the end of the backward / before a bucket's all-reduce)
-                _lib.wait_for(side)
-                with torch.cuda.stream(side):
-                    ws1 = WS.get(WS_LINEAR, x.device, 1)
-                    call(fn, *dw_args(ws1))
-                for t in (*srcs, x, *xin):   # xin: the folded input's BatchNorm, read by the staging
-                    t.record_stream(side)
+            if x16:     # the staged rows as the input operand, read as 16-byte segments
+                fn, lead = "vt_conv1d_bwd_weight_bf16_x16", (ptr(dy), dys, ptr(x))
+            elif inb:   # the previous block's BatchNorm + act applied in the staging (no fp32 dy)
+                fn, lead = "vt_conv1d_bwd_weight_bf16_in", (None, ptr(dy), dys, ptr(x), *inb)
+            elif bwd16:
+                fn, lead = "vt_conv1d_bwd_weight_bf16_dy16s", (ptr(dy), dys, ptr(x))
+            elif fused:
+                fn, lead = "vt_conv1d_bwd_weight_bf16_dy16", (ptr(dy), ptr(x))
             else:
+                fn, lead = "vt_conv1d_bwd_weight_bf16" if bf16 else "vt_conv1d_direct_bwd_weight", (ptr(dy), ptr(x))
+
+            def dw():
                 ws1 = WS.get(WS_LINEAR, x.device, 1)
-                call(fn, *dw_args(ws1))
+                call(fn, *lead, B, L, Cin, Cout, K, mode, up, ptr(pw.out[0]), pw.acc, ptr(ws1), ws1.numel(), _st())
+
+            # the weight gradient is off the data-gradient chain: compute it on a
+            # side stream (written in place into the flat gradient buffer, joined
+            # at the end of the backward / before a bucket's all-reduce)
+            # (xin: the folded input's BatchNorm, read by the staging)
+            _on_grad_stream(GRAD_STREAM if pw.direct else None, (dy, x, *xin), dw)
         gw, = pw.result()
         gg, gb = pbn.result()
-        return gx, gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None, None
+        return (gx, gw, gg, gb) + (None,) * 12
 
 
 class SyncConvBNActF(torch.autograd.Function):
@@ -890,19 +891,10 @@ class SyncConvBNActF(torch.autograd.Function):
             raise RuntimeError("SyncBatchNorm conv blocks cannot be captured into a hipGraph "
                                "(cross-rank statistics need a collective inside the step); train them eagerly")
         _check(x, w, g, b)
-        B, L, Cin = x.shape
-        Cout, _, K = w.shape
         x = x.contiguous()
-        Lo = _lib.lib().fns["vt_conv1d_out_len"](L, K, mode, up)
-        conv = torch.empty((B, Lo, Cout), device=x.device)
-        if bf16:
-            _h16(bf16)
-            w16, w16t = _conv_shadow(w)
-            call("vt_conv1d_fwd_bf16", ptr(x), B, L, Cin, ptr(w16), Cout, K, mode, up, ptr(conv), _st())
-        else:
-            w16t = None
-            call("vt_conv1d_direct_fwd", ptr(x), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(conv), _st())
-        M = B * Lo
+        conv, w16t = _conv_fwd(x, w, mode, up, bf16)
+        Cout = w.shape[0]
+        M = conv.shape[0] * conv.shape[1]
         mean = torch.empty(Cout, device=x.device)
         rstd = torch.empty(Cout, device=x.device)
         sums = torch.empty(2 * Cout + 1, dtype=torch.float64, device=x.device)
@@ -960,7 +952,7 @@ class SyncConvBNActF(torch.autograd.Function):
                  _st())
         gw, = pw.result()
         gg, gb = pbn.result()
-        return gx, gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None
+        return (gx, gw, gg, gb) + (None,) * 9
 
 
 def sync_conv_bn_act(x, w, g, b, run_mean, run_var, mode, up=False, act="relu", momentum=0.9, eps=1e-5, bf16=False,
@@ -975,23 +967,42 @@ def conv_bn_eval(x, w, g, b, run_mean, run_var, mode, up=False, act="relu", eps=
     _check(x, w, g, b)
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         raise RuntimeError("eval-mode conv blocks are inference-only (run under torch.no_grad())")
-    B, L, Cin = x.shape
-    Cout, _, K = w.shape
-    x = x.contiguous()
-    Lo = _lib.lib().fns["vt_conv1d_out_len"](L, K, mode, up)
-    conv = torch.empty((B, Lo, Cout), device=x.device)
-    if bf16:
-        _h16(h16_flag(bf16))
-        w16, _ = _conv_shadow(w)
-        call("vt_conv1d_fwd_bf16", ptr(x), B, L, Cin, ptr(w16), Cout, K, mode, up, ptr(conv), _st())
-    else:
-        call("vt_conv1d_direct_fwd", ptr(x), B, L, Cin, ptr(w), Cout, K, mode, up, ptr(conv), _st())
+    conv, _ = _conv_fwd(x.contiguous(), w, mode, up, h16_flag(bf16))
+    B, Lo, Cout = conv.shape
     call("vt_batchnorm_eval", ptr(conv), B * Lo, Cout, ptr(run_mean), ptr(run_var), eps, ptr(g), ptr(b), ACT[act],
          ptr(conv), _st())
     return conv
 
 
 # ---------------------------------------------------------------------- LSTM
+# what a layer saves for its backward: its input, h_{t-1} (the fp32 kernels) or h itself (the 16-bit
+# kernels, whose weight gradient reads it shifted by one step), the cell state and the gates
+_LstmLayer = collections.namedtuple("_LstmLayer", "inp hp c gates")
+# a layer's parameter gradients waiting for their launch: dg its dgates (fmt: as the recurrence's
+# bf16 image), pg their destinations; batched: one of the layers of a vt_lstm16_bwd_weight_multi call
+_LstmGrad = collections.namedtuple("_LstmGrad", "batched l dg fmt rec pg")
+
+
+def _lstm_plan(ins, S, half):
+    """The launches of an LSTM forward over layers of input sizes `ins`, in order: ("quad", 0)
+    (four 16-bit layers, vt_lstm16_quad_fwd), ("pair", l) (layers l and l + 1, vt_lstm16_pair_fwd),
+    ("l16", l) (one 16-bit layer) or ("fp32", l).  The backward walks the same groups in reverse."""
+    plan, l = [], 0
+    while l < len(ins):
+        l16 = half and ins[l] <= 64 and ins[l] % 4 == 0   # the layer runs on the 16-bit kernels
+        paired = l16 and LSTM_PAIR and _l16_pair_fits(S)
+        if paired and LSTM_CHAIN_FWD and l == 0 and len(ins) == 4:
+            plan.append(("quad", l))
+            l += 4
+        elif paired and l + 1 < len(ins):
+            plan.append(("pair", l))
+            l += 2
+        else:
+            plan.append(("l16" if l16 else "fp32", l))
+            l += 1
+    return plan
+
+
 class LSTMF(torch.autograd.Function):
     """Multi-layer unidirectional LSTM, batch_first, zero initial state.
     params: flat list [w_ih_l0, w_hh_l0, b_ih_l0, b_hh_l0, w_ih_l1, ...]."""
@@ -1002,18 +1013,16 @@ class LSTMF(torch.autograd.Function):
         B, S, _ = x.shape
         nl = len(params) // 4
         H = params[1].shape[1]
-        saved = []
-        pairs = []   # lower layers of the layer pairs run by vt_lstm16_pair_fwd
+        plan = _lstm_plan([x.shape[-1]] + [H] * (nl - 1), S, half)
+        recs = []   # one _LstmLayer per layer
         inp = x.contiguous()
-        l = 0
-        while l < nl:
+        for kind, l in plan:
             w_ih, w_hh, b_ih, b_hh = params[4 * l: 4 * l + 4]
             In = inp.shape[-1]
             h = torch.empty((B, S, H), device=x.device)
             c = torch.empty_like(h)
             gates = torch.empty((B, S, 4 * H), device=x.device)
-            h16 = half and In <= 64 and In % 4 == 0
-            if h16 and LSTM_PAIR and LSTM_CHAIN_FWD and l == 0 and nl == 4 and H == 64 and _l16_pair_fits(S):
+            if kind == "quad":
                 # all four layers in one launch: pair (2, 3) consumes layer 1's h chunk by chunk
                 hs = [h] + [torch.empty_like(h) for _ in range(3)]
                 cs = [c] + [torch.empty_like(h) for _ in range(3)]
@@ -1021,13 +1030,9 @@ class LSTMF(torch.autograd.Function):
                 pv = (ctypes.c_void_p * 16)(*[ptr(t) for t in params])
                 ov = (ctypes.c_void_p * 12)(*[ptr(t) for i in range(4) for t in (hs[i], cs[i], gs[i])])
                 call("vt_lstm16_quad_fwd", ptr(inp), In, ctypes.addressof(pv), B, S, H, ctypes.addressof(ov), _st())
-                saved += [inp, hs[0], cs[0], gs[0], hs[0], hs[1], cs[1], gs[1],
-                          hs[1], hs[2], cs[2], gs[2], hs[2], hs[3], cs[3], gs[3]]
-                pairs += [0, 2]
+                recs += [_LstmLayer(*r) for r in zip([inp] + hs[:3], hs, cs, gs)]
                 inp = hs[3]
-                l = 4
-                continue
-            if h16 and LSTM_PAIR and l + 1 < nl and H <= 64 and _l16_pair_fits(S):
+            elif kind == "pair":
                 # layers l and l + 1 in one launch (the upper one chunk behind the lower)
                 w_ih1, w_hh1, b_ih1, b_hh1 = params[4 * l + 4: 4 * l + 8]
                 h1, c1 = torch.empty_like(h), torch.empty_like(h)
@@ -1035,242 +1040,173 @@ class LSTMF(torch.autograd.Function):
                 call("vt_lstm16_pair_fwd", ptr(inp), In, ptr(w_ih), ptr(b_ih), ptr(w_hh), ptr(b_hh), ptr(w_ih1),
                      ptr(b_ih1), ptr(w_hh1), ptr(b_hh1), B, S, H, ptr(h), ptr(c), ptr(gates), ptr(h1), ptr(c1),
                      ptr(gates1), _st())
-                saved += [inp, h, c, gates, h, h1, c1, gates1]
-                pairs.append(l)
+                recs += [_LstmLayer(inp, h, c, gates), _LstmLayer(h, h1, c1, gates1)]
                 inp = h1
-                l += 2
-                continue
-            if h16:
+            elif kind == "l16":
                 # 16-bit MFMA recurrence over sample tiles (f16 operands, fp32 state); no h_{t-1}
-                # output: the weight gradient reads it from h (vt_lstm16_layer_bwd_weight)
+                # output: the weight gradient reads it from h (vt_lstm16_bwd_weight_multi)
                 call("vt_lstm16_layer_fwd", ptr(inp), In, ptr(w_ih), ptr(b_ih), ptr(w_hh), ptr(b_hh), B, S, H, ptr(h),
                      None, ptr(c), ptr(gates), _st())
-                saved += [inp, h, c, gates]
+                recs.append(_LstmLayer(inp, h, c, gates))
                 inp = h
-                l += 1
-                continue
-            hp = torch.empty_like(h)
-            if LSTM_FUSED and In <= 64:
-                # input projection inside the recurrence kernel (bitwise the unfused result)
-                call("vt_lstm_layer_fwd_x", ptr(inp), In, ptr(w_ih), ptr(b_ih), ptr(w_hh), ptr(b_hh), B, S, H, ptr(h),
-                     ptr(hp), ptr(c), ptr(gates), _st())
             else:
-                # gin = X W_ih^T + b_ih, overwritten in place by the post-activation gates
-                call("vt_linear_fwd", ptr(inp), B * S, In, ptr(w_ih), 4 * H, ptr(b_ih), ptr(gates), _st())
-                call("vt_lstm_layer_fwd", ptr(gates), ptr(w_hh), ptr(b_hh), B, S, H, ptr(h), ptr(hp), ptr(c),
-                     ptr(gates), _st())
-            saved += [inp, hp, c, gates]
-            inp = h
-            l += 1
-        ctx.save_for_backward(*saved)
+                hp = torch.empty_like(h)
+                if LSTM_FUSED and In <= 64:
+                    # input projection inside the recurrence kernel (bitwise the unfused result)
+                    call("vt_lstm_layer_fwd_x", ptr(inp), In, ptr(w_ih), ptr(b_ih), ptr(w_hh), ptr(b_hh), B, S, H,
+                         ptr(h), ptr(hp), ptr(c), ptr(gates), _st())
+                else:
+                    # gin = X W_ih^T + b_ih, overwritten in place by the post-activation gates
+                    call("vt_linear_fwd", ptr(inp), B * S, In, ptr(w_ih), 4 * H, ptr(b_ih), ptr(gates), _st())
+                    call("vt_lstm_layer_fwd", ptr(gates), ptr(w_hh), ptr(b_hh), B, S, H, ptr(h), ptr(hp), ptr(c),
+                         ptr(gates), _st())
+                recs.append(_LstmLayer(inp, hp, c, gates))
+                inp = h
+        ctx.save_for_backward(*[t for r in recs for t in r])
         ctx.params = params
-        ctx.nl = nl
-        ctx.half = bool(half)
-        ctx.pairs = pairs
+        ctx.plan = plan
         return inp
 
     @staticmethod
     def backward(ctx, gy):
         saved, params = ctx.saved_tensors, ctx.params
-        nl = ctx.nl
+        recs = [_LstmLayer(*saved[i: i + 4]) for i in range(0, len(saved), 4)]
         gy = gy.contiguous()
         B, S, H = gy.shape
         grads = [None] * len(params)
         dh = gy
         ws = WS.get(WS_LINEAR, gy.device, 1)
         gx = None
-        deferred = []
-        batch = []   # 16-bit layers whose parameter gradients share one vt_lstm16_bwd_weight_multi call
+        pending = []   # _LstmGrad: parameter gradients queued behind their recurrence launch
 
-        def wgrad16_flush(final=False):
-            """the batched layers' parameter gradients in one call: at the end of the backward
-            when every one goes to an in-place sink and LSTM_GRAD_DEFER is set (then on the
-            weight-gradient side stream when there is one), else after their recurrence launch"""
-            if not batch:
+        def launch(es):
+            """the queued layers' parameter gradients: the batched 16-bit layers four to a call,
+            the others every gradient of a layer in one pass over its dgates"""
+            wsw = WS.get(WS_LINEAR, gy.device, 1)
+            if not es[0].batched:
+                for e in es:
+                    call("vt_lstm_layer_bwd_weight", ptr(e.dg), ptr(e.rec.inp), e.rec.inp.shape[-1], ptr(e.rec.hp),
+                         B, S, H, *[ptr(t) for t in e.pg.out], e.pg.acc, ptr(wsw), wsw.numel(), _st())
                 return
-            direct = all(e[5].direct for e in batch)
-            if direct and LSTM_GRAD_DEFER and not final:
-                return
-            side = LSTM_GRAD_STREAM if direct else None
-            on_side = side is not None and side.cuda_stream != _lib.stream()
-            if on_side:
-                _lib.wait_for(side)
-            for i in range(0, len(batch), 4):
-                grp = batch[i: i + 4]
+            for i in range(0, len(es), 4):
+                grp = es[i: i + 4]
                 n = len(grp)
-                dv = (ctypes.c_void_p * n)(*[ptr(e[1]) for e in grp])
-                fv = (ctypes.c_int * n)(*[int(e[2]) for e in grp])
-                xv = (ctypes.c_void_p * n)(*[ptr(e[3]) for e in grp])
-                iv = (ctypes.c_int * n)(*[e[3].shape[-1] for e in grp])
-                hv = (ctypes.c_void_p * n)(*[ptr(e[4]) for e in grp])
-                gv = (ctypes.c_void_p * (4 * n))(*[ptr(t) for e in grp for t in e[5].out])
-                av = (ctypes.c_int * n)(*[e[5].acc for e in grp])
-                with torch.cuda.stream(side if on_side else torch.cuda.current_stream()):
-                    ws_b = WS.get(WS_LINEAR, gy.device, 1)
-                    call("vt_lstm16_bwd_weight_multi", n, ctypes.addressof(dv), ctypes.addressof(fv),
-                         ctypes.addressof(xv), ctypes.addressof(iv), ctypes.addressof(hv), B, S, H,
-                         ctypes.addressof(gv), ctypes.addressof(av), ptr(ws_b), ws_b.numel(), _st())
-            for l, dg, _, inp, hp, pg in batch:
-                if on_side:
-                    for t in (dg, inp, hp):
-                        t.record_stream(side)
-                grads[4 * l: 4 * l + 4] = pg.result()
-            batch.clear()
+                dv = (ctypes.c_void_p * n)(*[ptr(e.dg) for e in grp])
+                fv = (ctypes.c_int * n)(*[int(e.fmt) for e in grp])
+                xv = (ctypes.c_void_p * n)(*[ptr(e.rec.inp) for e in grp])
+                iv = (ctypes.c_int * n)(*[e.rec.inp.shape[-1] for e in grp])
+                hv = (ctypes.c_void_p * n)(*[ptr(e.rec.hp) for e in grp])
+                gv = (ctypes.c_void_p * (4 * n))(*[ptr(t) for e in grp for t in e.pg.out])
+                av = (ctypes.c_int * n)(*[e.pg.acc for e in grp])
+                call("vt_lstm16_bwd_weight_multi", n, ctypes.addressof(dv), ctypes.addressof(fv),
+                     ctypes.addressof(xv), ctypes.addressof(iv), ctypes.addressof(hv), B, S, H,
+                     ctypes.addressof(gv), ctypes.addressof(av), ptr(wsw), wsw.numel(), _st())
 
-        def wgrad(l, dg, half, fmt=False):
-            """every parameter gradient of layer l from its dgates (in place / deferred / on the
-            weight-gradient side stream, as configured)"""
-            inp, hp = saved[4 * l], saved[4 * l + 1]
+        def flush(final=False):
+            """Launch what is queued and due.  The one policy: a call whose gradients all go to
+            in-place sinks waits, under LSTM_GRAD_DEFER, for the end of the backward (final) — after
+            the last layer's recurrence, so the layer-to-layer dh chain is not interrupted by it —
+            and any other runs right after its recurrence launch; either way on the
+            weight-gradient side stream when there is one and the sinks are in place (joined before
+            the bucket all-reduce / the end of the backward; same kernels and summation orders as
+            in line: the same bits).  The batched 16-bit layers are one call, held or launched as
+            a whole, and go first; then the per-layer calls in the order queued."""
+            held = lambda es: bool(LSTM_GRAD_DEFER and not final and all(e.pg.direct for e in es))
+            multi = [e for e in pending if e.batched]
+            for es in ([] if held(multi) else multi, [e for e in pending if not e.batched and not held([e])]):
+                if not es:
+                    continue
+                side = LSTM_GRAD_STREAM if all(e.pg.direct for e in es) else None
+                _on_grad_stream(side, [t for e in es for t in (e.dg, e.rec.inp, e.rec.hp)], lambda: launch(es))
+                for e in es:
+                    grads[4 * e.l: 4 * e.l + 4] = e.pg.result()
+                pending[:] = [e for e in pending if e.l not in {d.l for d in es}]
+
+        def wgrad(l, dg, l16, fmt=False):
+            """every parameter gradient of layer l from its dgates (dg fp32, or (fmt) the
+            recurrence's bf16 image): queued for flush(), or the two-GEMM form at once"""
+            rec = recs[l]
             w_ih, w_hh, b_ih, b_hh = params[4 * l: 4 * l + 4]
-            In = inp.shape[-1]
-            if half and H == 64:
-                # batched: dg fp32, or (fmt) the recurrence's bf16 image
-                batch.append((l, dg, fmt, inp, hp, _ParamGrads([w_ih, w_hh, b_ih, b_hh], [True] * 4)))
-                return
-            wfn = "vt_lstm16_layer_bwd_weight" if half else "vt_lstm_layer_bwd_weight"
-            if (LSTM_FUSED or half) and In + H + 1 <= 144:
-                # every parameter gradient of the layer in one pass over dg
-                pg = _ParamGrads([w_ih, w_hh, b_ih, b_hh], [True] * 4)
-                if pg.direct and LSTM_GRAD_DEFER:
-                    # in-place sinks: issued after the last layer's recurrence (below), so
-                    # the layer-to-layer dh chain is not interrupted by them
-                    deferred.append((dg, inp, In, hp, pg, wfn))
-                    return
-                side = LSTM_GRAD_STREAM if (pg.direct and LSTM_GRAD_STREAM is not None) else None
-                if side is not None and side.cuda_stream != _lib.stream():
-                    # off the layer-to-layer chain (in-place sinks; same kernels, same bits)
-                    _lib.wait_for(side)
-                    with torch.cuda.stream(side):
-                        ws_s = WS.get(WS_LINEAR, gy.device, 1)
-                        call(wfn, ptr(dg), ptr(inp), In, ptr(hp), B, S, H,
-                             *[ptr(t) for t in pg.out], pg.acc, ptr(ws_s), ws_s.numel(), _st())
-                    for t in (dg, inp, hp):
-                        t.record_stream(side)
-                else:
-                    call(wfn, ptr(dg), ptr(inp), In, ptr(hp), B, S, H,
-                         *[ptr(t) for t in pg.out], pg.acc, ptr(ws), ws.numel(), _st())
-                grads[4 * l: 4 * l + 4] = pg.result()
+            In = rec.inp.shape[-1]
+            if l16 or (LSTM_FUSED and In + H + 1 <= 144):
+                pending.append(_LstmGrad(l16, l, dg, fmt, rec, _ParamGrads([w_ih, w_hh, b_ih, b_hh], [True] * 4)))
                 return
             pw = _ParamGrads([w_ih, w_hh], [True, True])
             # b_ih and b_hh receive the same gradient (the sum of dg over rows), written
             # by one column sum per bias straight into its gradient sink (no device copy:
             # a memcpy node would not survive the native step executor, csrc/stepgraph.cpp)
             pb = _ParamGrads([b_ih, b_hh], [True, True])
-            side = LSTM_GRAD_STREAM if (pw.direct and LSTM_GRAD_STREAM is not None) else None
-            if side is not None and side.cuda_stream != _lib.stream():
-                # weight gradients (in-place sinks) off the recurrence chain on a side
-                # stream; the returned bias gradient stays here (same kernels and
-                # summation orders as the serial branch below: bitwise equal)
-                _lib.wait_for(side)
-                with torch.cuda.stream(side):
-                    ws_s = WS.get(WS_LINEAR, gy.device, 1)
-                    call("vt_linear_bwd_weight", ptr(dg), B * S, 4 * H, ptr(inp), In, ptr(pw.out[0]), None, pw.acc,
-                         ptr(ws_s), ws_s.numel(), _st())
-                    call("vt_linear_bwd_weight", ptr(dg), B * S, 4 * H, ptr(hp), H, ptr(pw.out[1]), None, pw.acc,
-                         ptr(ws_s), ws_s.numel(), _st())
-                for t in (dg, inp, hp):
-                    t.record_stream(side)
-            else:
-                call("vt_linear_bwd_weight", ptr(dg), B * S, 4 * H, ptr(inp), In, ptr(pw.out[0]), None, pw.acc,
-                     ptr(ws), ws.numel(), _st())
-                call("vt_linear_bwd_weight", ptr(dg), B * S, 4 * H, ptr(hp), H, ptr(pw.out[1]), None, pw.acc,
-                     ptr(ws), ws.numel(), _st())
+
+            def dw():
+                wsw = WS.get(WS_LINEAR, gy.device, 1)
+                for src, K, out in ((rec.inp, In, pw.out[0]), (rec.hp, H, pw.out[1])):
+                    call("vt_linear_bwd_weight", ptr(dg), B * S, 4 * H, ptr(src), K, ptr(out), None, pw.acc,
+                         ptr(wsw), wsw.numel(), _st())
+
+            # weight gradients (in-place sinks) off the recurrence chain on a side stream; the
+            # bias gradients stay here (same kernels and summation orders either way: bitwise equal)
+            _on_grad_stream(LSTM_GRAD_STREAM if pw.direct else None, (dg, rec.inp, rec.hp), dw)
             for gb in pb.out:
                 call("vt_colsum", ptr(dg), B * S, 4 * H, ptr(gb), pb.acc, ptr(ws), ws.numel(), _st())
             gw_ih, gw_hh = pw.result()
             grads[4 * l: 4 * l + 4] = [gw_ih, gw_hh, *pb.result()]
 
-        l = nl - 1
-        if LSTM_CHAIN_BWD and ctx.pairs == [0, 2] and nl == 4:
-            # the four layers' backward in one launch: layer 2's dX (dmid, the gradient at layer
-            # 1's outputs) handed to layers 1, 0 chunk by chunk (vt_lstm16_quad_bwd)
-            In0 = saved[0].shape[-1]
-            fmts = [_dg16(saved[4 * k].shape[-1]) for k in range(4)]
-            dgs = [_dgates(f, B, S, H, gy.device) for f in fmts]
-            dmid = torch.empty((B, S, H), device=gy.device)
-            need_dx = ctx.needs_input_grad[0]
-            gin = torch.empty((B, S, In0), device=gy.device) if need_dx else None
-            wv = (ctypes.c_void_p * 8)(*[ptr(params[4 * k + i]) for k in range(4) for i in (0, 1)])
-            gv = (ctypes.c_void_p * 8)(*[ptr(saved[4 * k + i]) for k in range(4) for i in (3, 2)])
-            dv = (ctypes.c_void_p * 4)(*[ptr(t) for t in dgs])
-            call("vt_lstm16_quad_bwd", ptr(dh), ctypes.addressof(wv), ctypes.addressof(gv), In0, B, S, H,
-                 ctypes.addressof(dv), ptr(dmid), ptr(gin) if need_dx else None, _st(),
-                 sum(int(f) << k for k, f in enumerate(fmts)))
-            for k in (3, 2, 1, 0):
-                wgrad(k, dgs[k], True, fmts[k])
-            wgrad16_flush()
-            if need_dx:
-                dh = gx = gin
-            l = -1
-        while l >= 0:
-            if l - 1 in ctx.pairs:
-                # layers l (upper) and l - 1 (lower) in one launch: the upper layer's dX goes
+        # the forward's groups in reverse, a quad as its two pairs; under LSTM_CHAIN_BWD the two
+        # pairs of a four-layer LSTM are again one launch, however the forward ran them
+        pairs4 = [("pair", 0), ("pair", 2)]
+        groups = pairs4 if ctx.plan == [("quad", 0)] else ctx.plan
+        if LSTM_CHAIN_BWD and groups == pairs4:
+            groups = [("quad", 0)]
+        for kind, l in reversed(groups):
+            In = recs[l].inp.shape[-1]
+            need_dx = l > 0 or ctx.needs_input_grad[0]
+            gin = torch.empty((B, S, In), device=gy.device) if need_dx else None
+            if kind == "quad":
+                # the four layers' backward in one launch: layer 2's dX (dmid, the gradient at layer
+                # 1's outputs) handed to layers 1, 0 chunk by chunk (vt_lstm16_quad_bwd)
+                fmts = [_dg16(r.inp.shape[-1]) for r in recs]
+                dgs = [_dgates(f, B, S, H, gy.device) for f in fmts]
+                dmid = torch.empty((B, S, H), device=gy.device)
+                wv = (ctypes.c_void_p * 8)(*[ptr(params[4 * k + i]) for k in range(4) for i in (0, 1)])
+                gv = (ctypes.c_void_p * 8)(*[ptr(t) for r in recs for t in (r.gates, r.c)])
+                dv = (ctypes.c_void_p * 4)(*[ptr(t) for t in dgs])
+                call("vt_lstm16_quad_bwd", ptr(dh), ctypes.addressof(wv), ctypes.addressof(gv), In, B, S, H,
+                     ctypes.addressof(dv), ptr(dmid), ptr(gin), _st(), sum(int(f) << k for k, f in enumerate(fmts)))
+                for k in (3, 2, 1, 0):
+                    wgrad(k, dgs[k], True, fmts[k])
+            elif kind == "pair":
+                # layers l (lower) and l + 1 (upper) in one launch: the upper layer's dX goes
                 # to the lower layer through LDS (vt_lstm16_pair_bwd)
-                lo = l - 1
-                inpL, _, cL, gatesL = saved[4 * lo: 4 * lo + 4]
-                _, _, cU, gatesU = saved[4 * l: 4 * l + 4]
-                InL = inpL.shape[-1]
-                fU, fL = _dg16(H), _dg16(InL)
+                lo, up = recs[l], recs[l + 1]
+                fU, fL = _dg16(H), _dg16(In)
                 dgU = _dgates(fU, B, S, H, gy.device)
                 dgL = _dgates(fL, B, S, H, gy.device)
-                need_dx = lo > 0 or ctx.needs_input_grad[0]
-                gin = torch.empty((B, S, InL), device=gy.device) if need_dx else None
-                call("vt_lstm16_pair_bwd", ptr(dh), ptr(gatesU), ptr(cU), ptr(params[4 * l + 1]), ptr(params[4 * l]),
-                     ptr(gatesL), ptr(cL), ptr(params[4 * lo + 1]), ptr(params[4 * lo]), InL, B, S, H, ptr(dgU),
-                     ptr(dgL), ptr(gin) if need_dx else None, _st(), int(fL) | int(fU) << 1)
-                wgrad(l, dgU, True, fU)
-                wgrad(lo, dgL, True, fL)
-                wgrad16_flush()
-                if need_dx:
-                    dh = gx = gin
-                l -= 2
-                continue
-            inp, hp, c, gates = saved[4 * l: 4 * l + 4]
-            w_ih, w_hh = params[4 * l], params[4 * l + 1]
-            In = inp.shape[-1]
-            half = ctx.half and In <= 64 and In % 4 == 0   # hp is then h (read shifted by one step)
-            dg = torch.empty((B, S, 4 * H), device=gy.device)
-            need_dx = l > 0 or ctx.needs_input_grad[0]
-            fused = LSTM_FUSED and In <= 64
-            gin = torch.empty((B, S, In), device=gy.device) if need_dx else None
-            if half:
-                # bf16-MFMA recurrence, dX = dG W_ih inside; dG in fp32 for the weight gradients
-                call("vt_lstm16_layer_bwd", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), ptr(w_ih), In, B, S, H, ptr(dg),
-                     ptr(gin) if need_dx else None, _st())
-            elif fused:
-                # dX = dG W_ih inside the recurrence kernel (bitwise the unfused result)
-                call("vt_lstm_layer_bwd_x", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), ptr(w_ih), In, B, S, H, ptr(dg),
-                     ptr(gin) if need_dx else None, _st())
+                call("vt_lstm16_pair_bwd", ptr(dh), ptr(up.gates), ptr(up.c), ptr(params[4 * l + 5]),
+                     ptr(params[4 * l + 4]), ptr(lo.gates), ptr(lo.c), ptr(params[4 * l + 1]), ptr(params[4 * l]), In,
+                     B, S, H, ptr(dgU), ptr(dgL), ptr(gin), _st(), int(fL) | int(fU) << 1)
+                wgrad(l + 1, dgU, True, fU)
+                wgrad(l, dgL, True, fL)
             else:
-                call("vt_lstm_layer_bwd", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), B, S, H, ptr(dg), _st())
-                if need_dx:
-                    call("vt_linear_bwd_data", ptr(dg), B * S, 4 * H, ptr(w_ih), In, ptr(gin), 0, _st())
-            wgrad(l, dg, half)
-            wgrad16_flush()
+                gates, c = recs[l].gates, recs[l].c
+                w_ih, w_hh = params[4 * l], params[4 * l + 1]
+                dg = torch.empty((B, S, 4 * H), device=gy.device)
+                if kind == "l16":
+                    # bf16-MFMA recurrence, dX = dG W_ih inside; dG in fp32 for the weight gradients
+                    call("vt_lstm16_layer_bwd", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), ptr(w_ih), In, B, S, H,
+                         ptr(dg), ptr(gin), _st())
+                elif LSTM_FUSED and In <= 64:
+                    # dX = dG W_ih inside the recurrence kernel (bitwise the unfused result)
+                    call("vt_lstm_layer_bwd_x", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), ptr(w_ih), In, B, S, H,
+                         ptr(dg), ptr(gin), _st())
+                else:
+                    call("vt_lstm_layer_bwd", ptr(dh), ptr(gates), ptr(c), ptr(w_hh), B, S, H, ptr(dg), _st())
+                    if need_dx:
+                        call("vt_linear_bwd_data", ptr(dg), B * S, 4 * H, ptr(w_ih), In, ptr(gin), 0, _st())
+                wgrad(l, dg, kind == "l16")
+            flush()
             if need_dx:
-                dh = gin
-                gx = gin
-            l -= 1
-        wgrad16_flush(final=True)
-        if deferred:
-            # the layers' parameter gradients after the whole recurrence chain, on the
-            # weight-gradient side stream when there is one (joined before the bucket
-            # all-reduce / the end of the backward), else in line; same kernels and
-            # summation orders as in line per layer: the same bits
-            side = LSTM_GRAD_STREAM
-            on_side = side is not None and side.cuda_stream != _lib.stream()
-            if on_side:
-                _lib.wait_for(side)
-            with torch.cuda.stream(side if on_side else torch.cuda.current_stream()):
-                ws_d = WS.get(WS_LINEAR, gy.device, 1)
-                for dg, inp, In, hp, pg, wfn in deferred:
-                    call(wfn, ptr(dg), ptr(inp), In, ptr(hp), B, S, H,
-                         *[ptr(t) for t in pg.out], pg.acc, ptr(ws_d), ws_d.numel(), _st())
-            for dg, inp, In, hp, pg, wfn in deferred:
-                if on_side:
-                    for t in (dg, inp, hp):
-                        t.record_stream(side)
-                pg.result()
+                dh = gx = gin
+        flush(final=True)
         return (gx, None, *grads)
 
 
