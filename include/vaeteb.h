@@ -349,6 +349,48 @@ int vt_te_latent_rows(const float* mu_c, const float* lv_q, const float* mu_y, c
  * replaces: the per-sample numpy metrics ref/model/graph_model.py:1606-1645 and :1842-1851      */
 int vt_recon_metrics_rows(const float* y, const float* pr, int64_t B, int K, int64_t n, float* out, void* stream);
 
+/* ------------------------------------------------- K-draw predictive distribution
+ * vaeteb/predictive.py, DESIGN.md §3g.  B recordings, K latent draws each, rows r = b*K + k; the decoder
+ * gives mu_k, lv_k (B*K, n) for the n raw samples y (B, n).  With d = y - mu_k:
+ *   l_ki     = -0.5*(log 2pi + lv + d*d*exp(-lv))            (float32 expression, widened to double)
+ *   mean     = sum_k mu / K            var_aleatoric = sum_k exp(lv) / K
+ *   var_epistemic = sum_k (mu - mean)^2 / K   (formed about the first draw: exactly 0 when the draws
+ *                                              coincide, clamped at 0)
+ *   logdens  = LSE_k l_ki - log K      pit = sum_k Phi(d*exp(-lv/2)) / K   (argument float32, Phi double)
+ * As the evaluation kernels above: fixed-order sums in double, no atomics, identical run to run, under
+ * any split of the recordings over calls and whatever the workspace held; a recording's results
+ * depend on that recording only.  All return VT_ERR_ARG before any device work for a bad size (K outside
+ * 1..64, bins outside 1..256, n_levels outside 0..8, B outside 1..65535) or a null pointer.
+ *
+ * Samples per workgroup of vt_pred_mixture_rows.  Its workspace holds
+ * B * ceil(n / tile) * (K + 3 + bins + n_levels) doubles.                                       */
+int vt_pred_tile(void);
+/* mu, lv (B, row_elems) read at row r / K, eps (B*K, row_elems): z = mu + eps*exp(0.5*lv), vt_te_latent_rows's
+ * expression (the same bits for mu_c = mu, mu_y = 0).  With the prior mu_p, lv_p (B, row_elems) (both or
+ * neither NULL) logw[r] = 0.5 * sum_j (lv - lv_p + eps^2 - (z - mu_p)^2 * exp(-lv_p)) = log p(z|y) - log q(z|x,y)
+ * of a posterior draw; without it logw[r] = 0 (draws from the prior itself).  One workgroup per row.
+ * replaces: SeqVaeTeb.reparameterize ref/model/vae_teb_model.py:1046-1050, once per draw; the importance
+ *           weight has no reference counterpart                                                   */
+int vt_pred_draw_rows(const float* mu, const float* lv, const float* eps, const float* mu_p, const float* lv_p,
+                      int64_t B, int K, int64_t row_elems, float* z, float* logw, void* stream);
+/* Per sample: mean, var_aleatoric, var_epistemic (B, n), and pit, logdens (B, n, each nullable).  Per
+ * (recording, tile) into ws: sum_i l_ki for every k, the sums of logdens, of
+ * 0.5*(log 2pi + log v + (y - mean)^2 / v) and of sqrt(v) (v = var_aleatoric + var_epistemic, in double),
+ * the counts of min(bins - 1, floor(pit * bins)) and of |pit - 0.5| <= levels[l] / 2 (levels: n_levels
+ * device doubles; a NaN pit is counted nowhere).  Grid (tiles, B); every workgroup runs over k with an
+ * online log-sum-exp per sample, so mu and lv are read once (float4 on 16-byte aligned rows, scalars
+ * otherwise: the same bits either way).
+ * replaces: K forwards, torch.stack, logsumexp, special.ndtr and histc on (B, K, n) tensors     */
+int vt_pred_mixture_rows(const float* y, const float* mu, const float* lv, int64_t B, int K, int64_t n, int bins,
+                         const double* levels, int n_levels, float* mean, float* var_aleatoric,
+                         float* var_epistemic, float* pit, float* logdens, double* ws, void* stream);
+/* One workgroup per recording adds the tile partials of ws in tile order: ll (B, K) = sum_i l_ki;
+ * out (B, 5) = {nll_mixture = -mean_i logdens, nll_moment, sharpness = mean_i sqrt(v),
+ * elbo = sum_k (ll + logw) / K, iwae = LSE_k (ll + logw) - log K}; pit_hist (B, bins) int32;
+ * coverage (B, n_levels) = counts / n.  logw (B*K, nullable: 0) as vt_pred_draw_rows wrote it.     */
+int vt_pred_finish(const double* ws, const float* logw, int64_t B, int K, int64_t n, int bins, int n_levels,
+                   float* out, float* ll, int* pit_hist, float* coverage, void* stream);
+
 /* ------------------------------------------------- windows -> recording timelines
  * Overlapping windows stitched into packed per-recording timelines (vaeteb/timeline.py): position p of
  * a packed timeline of `total` positions carries the running sums acc[p] (float32: sum of w*v),

@@ -887,6 +887,28 @@ class SeqVaeTeb(nn.Module):
         1510-1680): up_gain_sweep with the single gain 1, every result (B, 1)."""
         return self.up_gain_sweep(y_st, y_ph, x_ph, y_raw, gains=(1.0,), **kw)
 
+    def predictive(self, y_st=None, y_ph=None, x_ph=None, y_raw=None, frontend=None, x=None, **kw):
+        """The predictive distribution of every recording from K latent draws: mean, aleatoric and
+        epistemic variance per sample, mixture NLL, PIT histogram, coverage, sharpness, ELBO and the
+        importance-weighted bound: vaeteb.predictive.Predictive(self)(y_st, y_ph, x_ph, y_raw, **kw)
+        (n_samples, eps, source, bins, levels, return_samples, return_pit), kept for the next call.
+        With frontend=fe, x=windows (B, 2, N) in place of the four fields they are taken from fe(x),
+        as up_gain_sweep takes them.  Returns a PredictiveResult."""
+        from .predictive import Predictive
+        if (frontend is None) != (x is None):
+            raise ValueError("frontend= and x= go together")
+        if frontend is not None:
+            if any(t is not None for t in (y_st, y_ph, x_ph, y_raw)):
+                raise ValueError("give either the four fields or frontend= and x=, not both")
+            f = frontend(x)
+            y_st, y_ph, x_ph, y_raw = f["fhr_st"], f["fhr_ph"], f["fhr_up_ph"], f["fhr"]
+        elif any(t is None for t in (y_st, y_ph, x_ph, y_raw)):
+            raise ValueError("y_st, y_ph, x_ph and y_raw are all required (or frontend= and x=)")
+        pred = self.__dict__.get("_predictive")
+        if pred is None:
+            pred = self.__dict__["_predictive"] = Predictive(self)
+        return pred(y_st, y_ph, x_ph, y_raw, **kw)
+
     def score_recordings(self, frontend, windows, **kw):
         """Whole recordings: the kept windows of `windows` (a vaeteb.windows.RecordingWindows) scored
         and stitched into per-recording transfer-entropy and reconstruction timelines with
