@@ -434,6 +434,55 @@ int vt_timeline_finish(const float* acc, const float* wacc, const int* count, in
 int vt_timeline_metrics(const float* y, const float* recon, const int* count, const int64_t* base, int64_t R,
                         float* out, void* stream);
 
+/* ------------------------------------------------- classifier evaluation statistics
+ * The statistics of vaeteb/clseval.py over the class-1 probability p (W,) float32 of
+ * the kept windows: one launch per statistic, integer outputs only.  fire(j, t) = p[j] > thr[t], a
+ * strict float32 comparison, so a NaN p never fires (it counts as prediction 0) and p == thr does
+ * not fire.  Every sum is an integer sum: the results are exact, identical run to run and do not
+ * depend on what the output buffers held.  All three return VT_ERR_ARG before any device work for a
+ * bad size (W, R, Bt at or above 2^31, T above 2^24, G above 65535, strike < 1, mode outside 0..1)
+ * or a null pointer; an empty output (R, T, G or Bt of 0) is a no-op; W == 0 writes the empty
+ * statistic (first = -1, zero counts).  Indices read from device tables are range-checked by the
+ * kernels: no access leaves p / label / rec / mult whatever the tables hold.
+ *
+ * Windows per scan step of vt_cls_auc_ranks, and windows staged per pass by the other two (exported
+ * for the tests, which put tie groups across every span border and a recording across a chunk).   */
+int vt_cls_scan_span(void);
+int vt_cls_stage_chunk(void);
+/* first (R, T) int32.  rec_base (R+1) device int64: recording r owns the windows
+ * j = rec_base[r] .. rec_base[r+1]-1 of p, in ascending start; local index j' = j - rec_base[r].
+ *   mode 0 (consecutive): run = fire ? run + 1 : 0, the run restarting (run = 0 before the update)
+ *     at a window with ordinal[j] != ordinal[j-1] + 1 (ordinal (W,) int32, nullable: never): a
+ *     window the quality gate dropped breaks a run;
+ *   mode 1 (cumulative):  run = the number of firing windows up to and including j'.
+ * first[r, t] = the least j' with run >= strike, -1 if there is none.  A workgroup stages a chunk of
+ * one recording's p and restart flags in LDS once and its lanes run over thresholds; longer recordings
+ * are walked chunk by chunk with the state carried in registers.
+ * replaces: the 400-step pandas sweep of find_threshold_after_strike / apply_strike_labeling that
+ *           test_classifier_with_strike_and_fpr drives (ref/model/graph_model_refactored_cls.py:1130-1220) */
+int vt_cls_alarm_sweep(const float* p, int64_t W, const int64_t* rec_base, int64_t R, const int* ordinal,
+                       const float* thr, int T, int strike, int mode, int* first, void* stream);
+/* counts (G, T, 4) int32 = {tp, fp, tn, fn} of the windows with group[j] == g (group (W,) int32,
+ * nullable: every window in group 0; a value outside [0, G) is in no group) under the prediction
+ * fire(j, t) against label[j] != 0 (label (W,) uint8).
+ * replaces: the per-epoch groupby + confusion_matrix loop of analyze_and_plot_classification_metrics
+ *           (ref/utils/data_utils.py:1592-1621), once per threshold                               */
+int vt_cls_confusion(const float* p, const uint8_t* label, const int* group, int64_t W, int G, const float* thr, int T,
+                     int* counts, void* stream);
+/* out (Bt, G, 4) int64 = {gt, eq, P, N} of the weighted window set of every (replicate b, group g):
+ * window i has weight w_i = mult[b, rec[i]] (mult (Bt, R) int32, nullable: 1; rec (W,) int32), 0 when
+ * group[i] != g (nullable as above) or p is NaN;
+ *   gt = sum_{i pos, j neg} w_i w_j [p_i > p_j]   eq = the same with ==   P, N = the class weights,
+ * so that the AUC (ties at half weight) is (gt + eq/2) / (P N).  p_sorted (W,) ascending with NaN last
+ * and order (W,) int64, p_sorted[k] = p[order[k]] (one torch.sort).  One workgroup per (b, g) scans the
+ * order once in spans of vt_cls_scan_span() windows: block scans of the class weights below each
+ * position and of their values at the head of each tie group (a maximal run of equal p_sorted), the
+ * running sums and the open tie group carried from span to span.  O(W) per replicate.
+ * replaces: roc_curve + auc per group (ref/utils/data_utils.py:1542-1543, :1611-1612); the cluster
+ *           bootstrap has no reference counterpart                                                */
+int vt_cls_auc_ranks(const float* p_sorted, const int64_t* order, int64_t W, const uint8_t* label, const int* rec,
+                     const int* group, int G, const int* mult, int64_t Bt, int64_t R, int64_t* out, void* stream);
+
 /* ----------------------------------------------------------------- optimiser
  * Flat fp32 buffers: every parameter / gradient / moment is a view of one
  * contiguous allocation.                                                        */

@@ -682,6 +682,19 @@ class SeqVaeTebClassifier(nn.Module):
             out = self.forward(y_st, y_ph, x_ph)
         return (out["predictions"], out["probabilities"]) if return_probabilities else out["predictions"]
 
+    def evaluate_recordings(self, frontend, windows, **kw):
+        """Labelled recordings: the kept windows of `windows` (a vaeteb.windows.RecordingWindows)
+        scored on the posterior mean, then the strike-rule alarm sweep over thresholds, the
+        operating point for a target false-positive rate, window-level confusion counts per epoch
+        group and the AUC with a cluster-bootstrap interval:
+        vaeteb.clseval.ClassifierScorer(self, frontend)(windows, **kw), the scorer kept for the next
+        call with the same front-end.  Returns a ClassifierEvaluation."""
+        from .clseval import ClassifierScorer
+        scorer = self.__dict__.get("_classifier_scorer")
+        if scorer is None or scorer.frontend is not frontend:
+            scorer = self.__dict__["_classifier_scorer"] = ClassifierScorer(self, frontend)
+        return scorer(windows, **kw)
+
     def forward(self, y_st, y_ph, x_ph, labels=None, return_latent=False, eps=None):
         z = self.extract_latent_features(y_st, y_ph, x_ph, eps=eps)
         logits = self.classifier(z)
