@@ -84,6 +84,20 @@ int vt_fe_spectrum(const float* x, int64_t rows, int N, int n_pad, int pad_left,
  *           ref/model/graph_model.py:1443-1458 (_apply_circular_shift), :1322-1339                */
 int vt_fe_spectrum_rolled(const float* x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left,
                           int pad_mode, const int* shifts, int K, const void* tw, void* xhat, void* stream);
+/* The same for the rows [row0, row0 + rows) of a surrogate plan (vaeteb/tenull.py): xhat[i] = padded
+ * spectrum of the surrogate up channel of plan row pr = row0 + i,
+ *   u[j] = x[src[pr]*x_row_stride + m((j - shift[pr]) mod N)],
+ *   m(q) = perm[pr*nblk + q / block_len]*block_len + q % block_len  for q < nblk*block_len, nblk = N / block_len,
+ *   m(q) = q  in the tail, and everywhere when perm is null.
+ * x: the up channel of recording 0 of the WHOLE batch of B recordings and src absolute, so a chunk of
+ * rows may read recordings outside itself; src, shift: device int[>= row0 + rows], perm: device
+ * int[>= (row0 + rows)*nblk] or null; shift of any sign and magnitude.  A src outside [0, B) or a perm
+ * entry outside [0, nblk) is not followed (the sample reads as 0).  Same values into the same FFT as
+ * vt_fe_spectrum on the materialised row: the same bits.
+ * replaces: no reference counterpart (its shift analysis stops at an argmin, ref/model/graph_model.py:1414) */
+int vt_fe_spectrum_surrogate(const float* x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left,
+                             int pad_mode, const int* src, const int* shift, const int* perm, int block_len,
+                             int64_t row0, int64_t rows, const void* tw, void* xhat, void* stream);
 
 /* S0: phi-lowpass + 2^log2T decimation of the padded signal, as a short
  * correlation with h0 = ifft(phi_0) (even, radius taps each side).
@@ -482,6 +496,34 @@ int vt_cls_confusion(const float* p, const uint8_t* label, const int* group, int
  *           bootstrap has no reference counterpart                                                */
 int vt_cls_auc_ranks(const float* p_sorted, const int64_t* order, int64_t W, const uint8_t* label, const int* rec,
                      const int* group, int G, const int* mult, int64_t Bt, int64_t R, int64_t* out, void* stream);
+
+/* ------------------------------------------------- transfer-entropy surrogate test
+ * The kernels of vaeteb/tenull.py.  Rows r = b*K + k, variant k = 0 the observed
+ * uterine-pressure channel, k >= 1 its surrogates.
+ *
+ * vt_te_kl_rows per step, without the elementwise tensor: ts[r, s] = (float)(sum_l (double)kl[r,s,l] / L),
+ * te[r] = (float)(sum_{s,l} (double)kl[r,s,l] / (S*L)), kl vt_te_kl_rows's fp32 expression in its order;
+ * mu_c, lv_q (B*K, S, L), prior mu_y, lv_p (B, S, L) read at row r / K; ts (B*K, S), te (B*K).  One
+ * workgroup per row, a step per group of min(64, pow2 >= L) lanes, fixed-order sums in double, no
+ * atomics: identical run to run and under any split of the rows over calls.
+ * replaces: measure_transfer_entropy(reduce_mean=False) ref/model/vae_teb_model.py:1194-1226 + a
+ *           .mean(-1) and a .mean() over its (S, L) result, once per row                          */
+int vt_te_kl_steps(const float* mu_c, const float* lv_q, const float* mu_y, const float* lv_p, int64_t B, int K,
+                   int S, int L, float* ts, float* te, void* stream);
+/* Rank statistics of ts (B, K1, S) and te (B, K1), 2 <= K1 <= 4096, one workgroup per recording b;
+ * comparisons are float32 >=, which a NaN on either side never satisfies:
+ *   count_ge[b]           int32  #{k >= 1 : te[b,k] >= te[b,0]}
+ *   step_count_ge[b,s]    int32  #{k >= 1 : ts[b,k,s] >= ts[b,0,s]}
+ *   max_count_ge[b,s]     int32  #{k >= 1 : mx[b,k] >= ts[b,0,s]}, mx[b,k] = max_s ts[b,k,s] skipping NaN
+ *                                (the max-statistic correction over the steps of the window)
+ *   surr_mean, surr_sd[b] double mean and sd (ddof = 1; NaN for K1 = 2) of te[b, 1:], summed in k order
+ *   step_surr_mean[b,s]   float  (float)(sum_{k >= 1} (double)ts[b,k,s] / (K1 - 1)), in k order
+ *   group_sums[k]         double sum_b te[b,k] in b order (a second, one-thread-per-k launch)
+ * No atomics: identical run to run.  VT_ERR_ARG before any device work for a bad size or a null pointer.
+ * replaces: no reference counterpart                                                              */
+int vt_tenull_stats(const float* ts, const float* te, int64_t B, int K1, int S, int* count_ge, int* step_count_ge,
+                    int* max_count_ge, double* surr_mean, double* surr_sd, float* step_surr_mean,
+                    double* group_sums, void* stream);
 
 /* ----------------------------------------------------------------- optimiser
  * Flat fp32 buffers: every parameter / gradient / moment is a view of one

@@ -13,6 +13,9 @@
 // The transfer-entropy shift sweep (vaeteb/te.py) adds two forms over B x K (recording, shift) rows:
 //   vt_fe_spectrum_rolled  vt_fe_spectrum of the up channel rolled by each shift (a gather)
 //   vt_fe_pairs_split      vt_fe_pairs with the fhr operand per recording, the up operand per row
+// and the surrogate test of the transfer entropy (vaeteb/tenull.py) one more:
+//   vt_fe_spectrum_surrogate  vt_fe_spectrum of a surrogate up channel per row: source recording,
+//                          shift and block permutation read from a plan (a gather)
 // Reference: ref/kymatio/kymatio/scattering1d/core/scattering1d.py:197-399,
 // ref/hdf5_dataset/kymatio_phase_scattering.py:211-301 (+ :303-360 cross),
 // ref/hdf5_dataset/hdf5_dataset.py:18-137 (normalisation).
@@ -81,6 +84,51 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_spectrum_rolled(const float* 
         int q = s - sh;             // s in [0, N): q in (-N, N)
         if (q < 0) q += N;
         X[n] = make_float2(s < 0 ? 0.f : xr[q], 0.f);
+    }
+    __syncthreads();
+    float2* R = fft_lds<false>(X, Y, n_pad, tw, 1);
+    float2* o = xhat + row * n_pad;
+    for (int n = threadIdx.x; n < n_pad; n += blockDim.x) o[n] = R[n];
+}
+
+// k_fe_spectrum of a surrogate up channel per plan row (vaeteb/tenull.py): workgroup i takes plan row
+// pr = row0 + i and writes row i of xhat.  The surrogate's sample j is
+//   u[j] = x[src[pr]][m((j - shift[pr]) mod N)],
+//   m(q) = perm[pr][q / block_len] * block_len + q % block_len  below (N / block_len) * block_len,
+//   m(q) = q                                                    in the tail (and when perm is null),
+// so padded position n reads u[pad_src(n - pad_left)]: k_fe_spectrum_rolled with the recording, the
+// shift and a block permutation per row, and the same bits as k_fe_spectrum on the materialised row.
+// x is the up channel of recording 0 of the whole batch and src is absolute, so a row may read a
+// recording outside the chunk that is being computed.  A src outside [0, B) or a perm entry outside
+// [0, N / block_len) reads nothing: the sample is 0.
+__global__ __launch_bounds__(FE_THREADS) void k_fe_spectrum_surrogate(
+    const float* __restrict__ x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left, int pad_mode,
+    const int* __restrict__ src, const int* __restrict__ shift, const int* __restrict__ perm, int block_len,
+    int64_t row0, const float2* __restrict__ tw, float2* __restrict__ xhat) {
+    extern __shared__ __attribute__((aligned(16))) float2 sm[];
+    float2* X = sm;
+    float2* Y = sm + n_pad;
+    const int64_t row = blockIdx.x, pr = row0 + row;
+    const int sb = src[pr];
+    const bool ok = sb >= 0 && sb < B;
+    const float* xr = x + (ok ? sb : 0) * x_row_stride;
+    int sh = shift[pr] % N;         // any sign, any magnitude -> [0, N)
+    if (sh < 0) sh += N;
+    const int nblk = N / block_len, body = nblk * block_len;
+    const int* pm = perm != nullptr ? perm + pr * nblk : nullptr;
+    for (int n = threadIdx.x; n < n_pad; n += blockDim.x) {
+        const int s = pad_src(n - pad_left, N, pad_mode);
+        float v = 0.f;
+        if (ok && s >= 0) {
+            int q = s - sh;         // s in [0, N): q in (-N, N)
+            if (q < 0) q += N;
+            if (pm != nullptr && q < body) {
+                const int blk = q / block_len, p = pm[blk];
+                q = (p >= 0 && p < nblk) ? p * block_len + (q - blk * block_len) : -1;
+            }
+            if (q >= 0) v = xr[q];
+        }
+        X[n] = make_float2(v, 0.f);
     }
     __syncthreads();
     float2* R = fft_lds<false>(X, Y, n_pad, tw, 1);
@@ -1271,6 +1319,24 @@ int vt_fe_spectrum_rolled(const float* x, int64_t B, int64_t x_row_stride, int N
                        S(stream), x, x_row_stride, N, n_pad, pad_left, pad_mode, shifts, K, (const float2*)tw,
                        (float2*)xhat);
     VT_LAUNCH_CHECK("vt_fe_spectrum_rolled");
+    return VT_OK;
+}
+
+int vt_fe_spectrum_surrogate(const float* x, int64_t B, int64_t x_row_stride, int N, int n_pad, int pad_left,
+                             int pad_mode, const int* src, const int* shift, const int* perm, int block_len,
+                             int64_t row0, int64_t rows, const void* tw, void* xhat, void* stream) {
+    VT_CHECK_ARG(pow2(n_pad) && n_pad <= VT_FFT_MAX_LDS && n_pad >= N, "vt_fe_spectrum_surrogate: n_pad=%d", n_pad);
+    VT_CHECK_ARG(B > 0 && N > 1 && pad_mode >= 0 && pad_mode <= 2 && pad_left >= 0 && x_row_stride >= N,
+                 "vt_fe_spectrum_surrogate: B/N/pad/stride");
+    VT_CHECK_ARG(block_len >= 1 && block_len <= N, "vt_fe_spectrum_surrogate: block_len=%d outside [1, N]", block_len);
+    VT_CHECK_ARG(row0 >= 0 && rows > 0 && rows < (1ll << 31) && row0 < (1ll << 40),
+                 "vt_fe_spectrum_surrogate: row0/rows");
+    VT_CHECK_ARG(x != nullptr && src != nullptr && shift != nullptr && tw != nullptr && xhat != nullptr,
+                 "vt_fe_spectrum_surrogate: null pointer");
+    hipLaunchKernelGGL(k_fe_spectrum_surrogate, dim3((unsigned)rows), dim3(FE_THREADS), fft_lds_bytes(n_pad),
+                       S(stream), x, B, x_row_stride, N, n_pad, pad_left, pad_mode, src, shift, perm, block_len, row0,
+                       (const float2*)tw, (float2*)xhat);
+    VT_LAUNCH_CHECK("vt_fe_spectrum_surrogate");
     return VT_OK;
 }
 

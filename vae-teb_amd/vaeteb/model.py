@@ -853,6 +853,17 @@ class SeqVaeTeb(nn.Module):
             sweep = self.__dict__["_shift_sweep"] = ShiftSweep(self, frontend)
         return sweep(x, left_shifts() if shifts is None else shifts, **kw)
 
+    def te_significance(self, frontend, x, rows_per_launch=256, **kw):
+        """Surrogate test of the transfer entropy of every recording of x (B, 2, N): the observed value
+        and every step of it ranked among K surrogate up channels (kind "shift", "block" or "swap", or
+        plan=): vaeteb.tenull.TeSignificance(self, frontend, rows_per_launch)(x, **kw), kept for the
+        next call with the same front-end.  Returns a TeSignificanceResult."""
+        from .tenull import TeSignificance
+        sig = self.__dict__.get("_te_significance")
+        if sig is None or sig.frontend is not frontend or sig.rows_per_launch != int(rows_per_launch):
+            sig = self.__dict__["_te_significance"] = TeSignificance(self, frontend, rows_per_launch)
+        return sig(x, **kw)
+
     def up_gain_sweep(self, y_st=None, y_ph=None, x_ph=None, y_raw=None, gains=None, frontend=None, x=None, **kw):
         """Transfer entropy and reconstruction metrics (VAF / MSE / SNR of mu_pr against y_raw) of
         every recording under multiplicative gains on its normalised UP features

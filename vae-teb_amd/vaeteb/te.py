@@ -104,6 +104,33 @@ class ShiftSweep:
             return [(b0, min(per, B - b0), 0, K) for b0 in range(0, B, per)]
         return [(b, 1, k0, min(R, K - k0)) for b in range(B) for k0 in range(0, K, R)]
 
+    def _posterior_rows(self, xhat, an_fhr, c_lv, b0, nb, nk, x_ph=None):
+        """The posterior pieces (mu_c, lv_q), each (nb * nk, S, L), of the rows whose padded up spectra
+        are xhat (nb * nk, n_pad, 2): row i belongs to recording b0 + i // nk, whose fhr analytic
+        signals (an_fhr, all recordings) and c_logvar (c_lv, all recordings) it reads.  The up analytic
+        signals, the cross pairs, the normalised window (into x_ph when given, else a work buffer),
+        the source encoder and the conditional encoder; called inside the model's _PAR setting."""
+        fe, m = self.frontend, self.model
+        p = fe.plan
+        N, S, C_x, R = p.N, fe.S_out, fe.C_x, nb * nk
+        n_slots_i = fe.tab["n_slots"]
+        k_, mean_, std_ = fe.stats["fhr_up_ph"]
+        st = _lib.stream()
+        an_up = self._buf("analytic_up", (R, self.up_tab["n_slots"], N, 2))
+        launch_wavelet(p, xhat, R, 1, self.up_tab, an_up, None, 0)
+        pairs = self._buf("pairs", (R, C_x, p.pair_len))
+        _lib.call("vt_fe_pairs_split", an_fhr.data_ptr() + 8 * b0 * n_slots_i * N, n_slots_i,
+                  _lib.ptr(an_up), self.up_tab["n_slots"], nb, nk, N, p.n_pad, p.pad_left, C_x,
+                  _lib.ptr(self.slot_i), _lib.ptr(self.slot_j), _lib.ptr(self.power), _lib.ptr(p.t_tw),
+                  _lib.ptr(p.t_phi_crop), p.dec, p.pair_start, p.pair_len, 0, _lib.ptr(pairs), st)
+        if x_ph is None:
+            x_ph = self._buf("x_ph", (R, S, C_x))
+        _lib.call("vt_fe_normalize_window", _lib.ptr(pairs), R, C_x, C_x, p.S, fe.trim, S, _lib.ptr(k_),
+                  _lib.ptr(mean_), _lib.ptr(std_), 1e-6, _lib.ptr(x_ph), C_x, 0, st)
+        mu_x = m.source_encoder(x_ph)
+        c_rep = c_lv[b0:b0 + nb].unsqueeze(1).expand(nb, nk, S, c_lv.shape[-1]).reshape(R, S, -1)
+        return m.conditional_encoder(mu_x, c_rep)
+
     @torch.no_grad()
     def __call__(self, x, shifts, elementwise=False, return_features=False):
         fe, m = self.frontend, self.model
@@ -116,12 +143,10 @@ class ShiftSweep:
         S, C_x = fe.S_out, fe.C_x
         feats = fe(x)                                   # fhr side, once; leaves the fhr analytic signals
         an_fhr = fe._bufs["analytic"]                   # (B, n_slots, N, 2)
-        n_slots_i = fe.tab["n_slots"]
         m.eval()
         if getattr(m, "h16_format", None):
             _lib.set_h16(m.h16_format == "fp16")
         x_ph_all = torch.empty((B, K, S, C_x), device=p.device) if return_features else None
-        k_, mean_, std_ = fe.stats["fhr_up_ph"]
         st = _lib.stream()
         prev = dict(_model._PAR)
         _model._PAR["on"], _model._PAR["next"] = bool(m.concurrent_encoders), 1
@@ -137,20 +162,8 @@ class ShiftSweep:
                 xhat = self._buf("xhat", (R, p.n_pad, 2))
                 _lib.call("vt_fe_spectrum_rolled", x.data_ptr() + 4 * ((b0 * 2 + 1) * N), nb, 2 * N, N, p.n_pad,
                           p.pad_left, 0, sh_dev.data_ptr() + 4 * k0, nk, _lib.ptr(p.t_tw), _lib.ptr(xhat), st)
-                an_up = self._buf("analytic_up", (R, self.up_tab["n_slots"], N, 2))
-                launch_wavelet(p, xhat, R, 1, self.up_tab, an_up, None, 0)
-                pairs = self._buf("pairs", (R, C_x, p.pair_len))
-                _lib.call("vt_fe_pairs_split", an_fhr.data_ptr() + 8 * b0 * n_slots_i * N, n_slots_i,
-                          _lib.ptr(an_up), self.up_tab["n_slots"], nb, nk, N, p.n_pad, p.pad_left, C_x,
-                          _lib.ptr(self.slot_i), _lib.ptr(self.slot_j), _lib.ptr(self.power), _lib.ptr(p.t_tw),
-                          _lib.ptr(p.t_phi_crop), p.dec, p.pair_start, p.pair_len, 0, _lib.ptr(pairs), st)
-                x_ph = (x_ph_all.view(B * K, S, C_x)[r0:r0 + R] if return_features
-                        else self._buf("x_ph", (R, S, C_x)))
-                _lib.call("vt_fe_normalize_window", _lib.ptr(pairs), R, C_x, C_x, p.S, fe.trim, S, _lib.ptr(k_),
-                          _lib.ptr(mean_), _lib.ptr(std_), 1e-6, _lib.ptr(x_ph), C_x, 0, st)
-                mu_x = m.source_encoder(x_ph)
-                c_rep = c_lv[b0:b0 + nb].unsqueeze(1).expand(nb, nk, S, c_lv.shape[-1]).reshape(R, S, -1)
-                mu_c, lv_q = m.conditional_encoder(mu_x, c_rep)
+                x_ph = (x_ph_all.view(B * K, S, C_x)[r0:r0 + R] if return_features else None)
+                mu_c, lv_q = self._posterior_rows(xhat, an_fhr, c_lv, b0, nb, nk, x_ph)
                 _lib.call("vt_te_kl_rows", _lib.ptr(mu_c), _lib.ptr(lv_q), mu_y.data_ptr() + 4 * b0 * S * L,
                           lv_p.data_ptr() + 4 * b0 * S * L, nb, nk, S * L, te.data_ptr() + 4 * r0,
                           kl.data_ptr() + 4 * r0 * S * L if elementwise else None, st)
